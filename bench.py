@@ -1,8 +1,21 @@
 """Headline benchmark: frames/sec/GPU of HMMR's inference hot path on MI355X.
 
     python bench.py [--gpus N] [--steps K] [--warmup W] [--frames 256] [--dtype f16x3] [--video-frames V]
+                    [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
         --master-port P bench.py --gpus N --steps K --warmup W
+
+A plain run does only what the headline needs: set up, the initialisation call, W warm-up steps, K timed steps, the
+outputs of the last timed step when `--dump-outputs DIR` is given, and the result line (`value`, `ms_per_step`, ...).
+Every other leg described below -- `modes`, the end-to-end error against the oracle, `stress`, `roofline`,
+`by_config`, `fps_sustained_2s` / `power`, the PCIe-inclusive rates, `cpu_baseline`, `smpl_verts_max_abs_err` and, with
+N > 1, the gather / scaling-efficiency measurements -- runs only with `--full` (their `--no-*` switches still apply
+there); in a plain line their fields are null or absent.
+
+`--dump-outputs DIR` writes what the last timed step computed -- the per-frame arrays a caller of the path receives
+(`cams`, `joints`, `kps`, `poses`, `shapes`, `verts`, `omegas` and their `_delta` forms) -- as DIR/<name>.npy in
+float32.  When all frames together exceed 64 MB, every array holds the same fixed, seeded sample of frames (ascending;
+listed in the line's `dump_outputs.frames`).  The inputs (seeded weights and video) are the same from run to run.
 
 Workload (BASELINE.json configs[3], the configuration the metric
 "frames/sec/GPU (ResNet+temporal+SMPL, 224x224)" is quoted on): each GPU takes a
@@ -63,6 +76,8 @@ ERR_WINDOW_START = 96                    # output frames [96, 104) are checked e
 # the headline's own check: four windows spread over the step's output frames -- the first (its leading frames are the reference's zero
 # padding images), two in the middle, and the last (trailing padding)
 ERR_WINDOW_STARTS = (0, 96, 176, 248)
+DUMP_BYTES = 64 * 10 ** 6                # --dump-outputs: at most this much in all
+DUMP_SEED = 0                            # ... and the seed of the frame sample beyond it
 
 
 class Cfg(object):
@@ -234,9 +249,11 @@ def multi_gpu_fields(tester, n_total, span, world, rank, device, reps=3, pipelin
     return out
 
 
-def run_mode(dtype, args, world, rank, device, weights, smpl, span, n_total, steps, warmup, sustain_s=0.0, tester=None):
+def run_mode(dtype, args, world, rank, device, weights, smpl, span, n_total, steps, warmup, sustain_s=0.0, tester=None,
+             on_timed=None):
     """Time `steps` passes of the hot path in operand mode `dtype`.  Returns the timing dict, the
-    tester / predictor (for the roofline leg) and the last output tensor."""
+    tester / predictor (for the roofline leg) and the last output tensor.  `on_timed(out, tester)` is called with the
+    output of the last timed step right after the timed region (before the sustained leg re-uses its buffer)."""
     from human_dynamics_amd import dist as hd
     from human_dynamics_amd.evaluation.tester import Tester
     if tester is None:
@@ -285,6 +302,8 @@ def run_mode(dtype, args, world, rank, device, weights, smpl, span, n_total, ste
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         elapsed = float(t.item())
     assert out.shape[0] == n_total and bool(torch.isfinite(out[:, :1000]).all())
+    if on_timed is not None:
+        on_timed(out, tester)
     timing = {"fps": n_total * steps / elapsed, "ms_per_step": elapsed / steps * 1e3, "steps": steps,
               "pipeline": pipeline, "resnet_streams": eng.resnet_streams,
               "step_streams": getattr(predictor, "step_streams", None) is not None}
@@ -324,6 +343,30 @@ def e2e_errors(out, tester, ref, sliced=False, starts=(ERR_WINDOW_START,)):
     layout, _ = hd.record_layout(len(tester.delta_t_values))
     rec = hd.unpack_outputs(out if sliced else rows_of(out, starts), layout)
     return {"e2e_%s_max_abs_err" % k: float(np.abs(rec[k].cpu().numpy() - ref[k]).max()) for k in ("verts", "joints", "omegas")}
+
+
+def dump_outputs(out, tester, path, budget=DUMP_BYTES, seed=DUMP_SEED):
+    """Write the packed records `out` [n_frames, rec_len] of one step as the per-frame arrays a caller of the path receives,
+    path/<name>.npy in float32.  Beyond `budget` bytes every array keeps the same fixed, seeded sample of frames (ascending).
+    -> what the line says about it."""
+    from human_dynamics_amd import dist as hd
+    layout, rec_len = hd.record_layout(len(tester.delta_t_values))
+    n = out.shape[0]
+    per_frame = rec_len * 4 + 2 * len(layout)          # (the .npy headers, ~128 B per file, budgeted as 2 B per frame and file)
+    rows = None
+    if n * per_frame > budget:
+        rows = np.sort(np.random.default_rng(seed).choice(n, budget // per_frame, replace=False))
+        out = out[torch.as_tensor(rows, device=out.device)]
+    host = out.float().cpu().numpy()
+    os.makedirs(path, exist_ok=True)
+    written = 0
+    for k, v in hd.unpack_outputs(host, layout).items():
+        v = np.ascontiguousarray(v, dtype=np.float32)
+        np.save(os.path.join(path, k + ".npy"), v)
+        written += v.nbytes
+    return {"dir": path, "arrays": sorted(k for k, _, _, _ in layout), "dtype": "float32", "bytes": written,
+            "frames_total": n, "frames": None if rows is None else [int(r) for r in rows],
+            "sample": None if rows is None else "%d of %d frames, numpy default_rng(%d).choice, ascending" % (len(rows), n, seed)}
 
 
 def stress_leg(span, span_host, plan, n_total, smpl, device):
@@ -771,13 +814,21 @@ def main():
                          "(hidden under the next step); one video (--video-frames, the N > 1 default) -> theta.  Both modes are "
                          "measured after the timed region (`single_video_ms_by_gather`, `gather_by_measurement`)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--sustain", type=float, default=2.0,
-                    help="seconds of a second, longer timed leg of the same steps (`fps_sustained_2s`; 0 = skip)")
+    ap.add_argument("--full", action="store_true",
+                    help="also run every leg beyond the headline (other operand modes, end-to-end error and stress checks, roofline, "
+                         "by_config, sustained leg and power, PCIe-inclusive rates, CPU baseline; N > 1: gather and scaling "
+                         "measurements).  Off: set up, warm up, time the steps, dump outputs, print the line")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the outputs of the last timed step as DIR/<name>.npy (float32; at most 64 MB in all, a fixed "
+                         "seeded sample of frames beyond that)")
+    ap.add_argument("--sustain", type=float, default=None,
+                    help="seconds of a second, longer timed leg of the same steps (`fps_sustained_2s`; 0 = skip; "
+                         "default 2 with --full, 0 without)")
     ap.add_argument("--no-by-config", action="store_true", help="skip the `by_config` legs (the other BASELINE sizes)")
     ap.add_argument("--no-power", action="store_true",
                     help="skip the power / clock sampling (SmiSampler's ~0.6 s of extra ResNet passes, the clock-probe wave): for runs under a profiler, "
                          "whose per-pass averages should be taken over the steps' own passes")
-    ap.add_argument("--by-config-only", action="store_true", help="run ONLY the `by_config` legs and print them as one JSON line (what the default run "
+    ap.add_argument("--by-config-only", action="store_true", help="run ONLY the `by_config` legs and print them as one JSON line (what a --full run "
                                                                   "starts as a child process; --dtype: the operand mode, not auto)")
     ap.add_argument("--no-pcie", action="store_true", help="skip the PCIe-inclusive leg (used for PMC passes)")
     ap.add_argument("--serial-gather", action="store_true",
@@ -854,10 +905,19 @@ def main():
     gather_requested = args.gather
     if args.gather == "auto":
         args.gather = "theta" if (world > 1 and strong) else "records"
+    full = args.full                                       # every leg beyond the headline; a plain run times the steps and stops
+    if args.sustain is None:
+        args.sustain = 2.0 if full else 0.0
+    dumped = {}
+
+    def keep_outputs(out_, tester_):
+        if rank == 0:
+            dumped.update(dump_outputs(out_, tester_, args.dump_outputs))
     timing, tester, predictor, out = run_mode(args.dtype, args, world, rank, device, weights, smpl, span, n_total,
-                                              args.steps, args.warmup, sustain_s=args.sustain)
+                                              args.steps, args.warmup, sustain_s=args.sustain,
+                                              on_timed=keep_outputs if args.dump_outputs else None)
     mg = None
-    if world > 1:
+    if world > 1 and full:
         mg = multi_gpu_fields(tester, n_total, span, world, rank, device, pipeline=False)
     value, ms_per_step = timing["fps"], timing["ms_per_step"]
     from human_dynamics_amd import precision
@@ -873,7 +933,7 @@ def main():
     # the same per-rank shard as a 1-GPU job (no collective), every rank at once: value / (world x this) = the scaling efficiency
     # of this run (the driver computes its own from the per-N lines)
     scaling_eff, shard_fps, rccl_ranks = None, None, None
-    if world > 1:
+    if world > 1 and full:
         rccl_ranks = mg["rccl_ranks"]
         n_loc = plan.o1 - plan.o0
         solo = hd.ShardedPredictor(tester, n_loc, 0, 1, pipeline=not (args.no_pipeline or args.graph or args.serial),
@@ -897,18 +957,20 @@ def main():
 
     result = None
     if rank == 0:
-        roofline = roofline_leg(tester, plan, span, args.dtype, args.frames if not strong else -1, power=not args.no_power)
-        # the overlapped reading of the same FLOPs: the timed steps run the ResNet passes of consecutive steps on two streams
-        roofline["achieved_overlapped"] = round(RESNET_FLOPS_PER_FRAME * (plan.f1 - plan.f0 + 1) / (ms_per_step * 1e-3) / 1e12, 2)
-        roofline["frac_overlapped"] = round(roofline["achieved_overlapped"] / roofline["peak"], 4)
-        roofline["achieved_overlapped_note"] = ("ResNet FLOPs of one step / ms_per_step (the step also carries the f_movie / IEF / "
-                                                "SMPL tail on a second stream): the figure `value` corresponds to")
+        roofline = None
+        if full:
+            roofline = roofline_leg(tester, plan, span, args.dtype, args.frames if not strong else -1, power=not args.no_power)
+            # the overlapped reading of the same FLOPs: the timed steps run the ResNet passes of consecutive steps on two streams
+            roofline["achieved_overlapped"] = round(RESNET_FLOPS_PER_FRAME * (plan.f1 - plan.f0 + 1) / (ms_per_step * 1e-3) / 1e12, 2)
+            roofline["frac_overlapped"] = round(roofline["achieved_overlapped"] / roofline["peak"], 4)
+            roofline["achieved_overlapped_note"] = ("ResNet FLOPs of one step / ms_per_step (the step also carries the f_movie / IEF / "
+                                                    "SMPL tail on a second stream): the figure `value` corresponds to")
         single = world == 1
         # the other BASELINE / reference sizes in a PROCESS OF THEIR OWN (`bench.py --by-config-only`): HIP streams share a few hardware
         # queues in creation order, and whichever of the two -- the headline's predictor (two step streams, tail stream) or these legs
         # (side streams of the two-part ResNet pass) -- comes second in one process reads 20-25 % slow (profiles/r06a, r06m, r06n)
         by_config = None
-        if single and not args.no_by_config:
+        if single and full and not args.no_by_config:
             import subprocess
             try:
                 r = subprocess.run([sys.executable, os.path.abspath(__file__), "--by-config-only", "--dtype", args.dtype],
@@ -927,7 +989,7 @@ def main():
         others, modes = {}, {}
         all_frames_diff = None
         err_starts = tuple(s0 for s0 in ERR_WINDOW_STARTS if s0 + 8 <= n_total) or (0,)
-        if single and not args.only_main:
+        if single and full and not args.only_main:
             for other in [m for m in ("f16x3", "bf16", "f32") if m != args.dtype]:
                 tm, t_o, pred_o, out_o = run_mode(other, args, world, rank, device, weights, smpl, span, n_total,
                                                   args.steps, args.warmup)
@@ -942,9 +1004,9 @@ def main():
                     del a_, b_
                 del pred_o, out_o
                 torch.cuda.empty_cache()
-        span_host = span.cpu().numpy() if single else None
+        span_host = span.cpu().numpy() if (single and full) else None
         ref = None
-        if single and not args.no_cpu_baseline and n_total >= ERR_WINDOW_START + 14:
+        if single and full and not args.no_cpu_baseline and n_total >= ERR_WINDOW_START + 14:
             ref = oracle_window(span_host, plan.f0, n_total, weights, smpl, err_starts)
             modes[args.dtype] = dict(fps=round(value, 1), ms_per_step=round(ms_per_step, 3), **e2e_errors(out, tester, ref, starts=err_starts))
             for other, (t_o, rows) in others.items():
@@ -983,7 +1045,7 @@ def main():
         pcie_fps = pcie_nov = pcie_sustained = pcie_u8_sustained = None
         pcie_long = pcie_u8 = pcie_u8_long = None
         pcie_other = {}
-        if single and not args.no_pcie:
+        if single and full and not args.no_pcie:
             pcie_fps, pcie_nov = pcie_rate(tester)
             if len(span_host) >= 256:            # a 4-chunk video: the streamed steady state (copies under the kernels)
                 pcie_long = pcie_rate(tester, np.concatenate([span_host[:256]] * 4))[0]
@@ -1059,6 +1121,8 @@ def main():
             "pcie_inclusive_fps_sustained": pcie_sustained, "pcie_inclusive_fps_sustained_uint8_input": pcie_u8_sustained,
             "pcie_inclusive_fps_uint8_input": pcie_u8, "pcie_inclusive_fps_uint8_input_1024_frame_video": pcie_u8_long,
         }
+        if args.dump_outputs:
+            result["dump_outputs"] = dumped
         if modes:
             result["modes"] = modes
             result["tolerance"] = tol
@@ -1074,7 +1138,7 @@ def main():
             result["pcie_inclusive_fps_bf16"] = pcie_other.get("bf16")
         if single and ref is not None and not args.no_stress and not args.only_main:
             result["stress"] = stress_leg(span, span_host, plan, n_total, smpl, device)
-        if not args.no_cpu_baseline and single:
+        if full and not args.no_cpu_baseline and single:
             result["cpu_baseline"] = cpu_baseline()
             # second half of the metric: SMPL-stage vertex error vs the float64 oracle on device-regressed theta
             # (the SMPL stage is fp32 in every operand mode)

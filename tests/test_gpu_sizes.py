@@ -223,6 +223,48 @@ def test_config5_4096_frame_video_on_one_gpu(weights, smpl_consts, gpu_device):
     assert js["config"]["resnet_frames_encoded_per_gpu"] == n + 1 and js["value"] > 2000
 
 
+def test_bench_plain_line_and_dump_outputs(weights, smpl_consts, gpu_device, tmp_path):
+    """A plain `bench.py` run: exactly --steps timed steps, `ms_per_step` consistent with `value`, none of the --full legs, and
+    --dump-outputs = the per-frame arrays of the last timed step (float32, at most 64 MB in all: a seeded sample of the 256
+    frames), which equal Tester.predict_all_images on the same seeded frames."""
+    import glob
+    import json
+    import os
+    import subprocess
+    import sys
+    from human_dynamics_amd import dist as hd
+    from human_dynamics_amd.evaluation.tester import Tester
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    d = str(tmp_path / "out")
+    r = subprocess.run([sys.executable, "bench.py", "--gpus", "1", "--steps", "3", "--warmup", "1", "--dtype", "f16x3",
+                        "--dump-outputs", d], cwd=root, capture_output=True, text=True, timeout=600)
+    lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
+    assert r.returncode == 0 and len(lines) == 1, r.stderr[-800:]
+    js = json.loads(lines[0])
+    assert js["steps"] == 3 and js["warmup"] == 1 and js["ms_per_step"] > 0 and js["frames_total"] == 256
+    assert js["value"] == pytest.approx(256 * 1e3 / js["ms_per_step"], rel=2e-3) and js["dtype"] == "f16x3"
+    assert js["roofline"] is None and js["by_config"] is None and js["fps_sustained_2s"] is None and js["pcie_inclusive_fps"] is None
+    assert not {"modes", "stress", "cpu_baseline", "smpl_verts_max_abs_err"} & set(js)
+    files = sorted(glob.glob(os.path.join(d, "*.npy")))
+    layout, _ = hd.record_layout(2)
+    assert sorted(os.path.basename(f)[:-4] for f in files) == sorted(k for k, _, _, _ in layout) == js["dump_outputs"]["arrays"]
+    assert sum(os.path.getsize(f) for f in files) <= 64 * 10 ** 6
+    rows = js["dump_outputs"]["frames"]
+    assert rows == sorted(set(rows)) and 0 < len(rows) < 256 and rows[-1] < 256
+    t = Tester(Config(batch_size=8), weights=weights, smpl=smpl_consts, dtype="f16x3", device=gpu_device)
+    plan = hd.ShardPlan(256, 8, 20, 13, 1, 0)
+    gen = torch.Generator(device=gpu_device)
+    gen.manual_seed(1234)                                      # bench.py's rank-0 span
+    span = torch.rand((plan.f1 - plan.f0, 224, 224, 3), generator=gen, device=gpu_device) * 2 - 1
+    ref = t.predict_all_images(span)
+    assert {"verts", "joints", "omegas", "verts_delta"} <= set(ref)
+    for k, v in ref.items():
+        got = np.load(os.path.join(d, k + ".npy"))
+        assert got.dtype == np.float32 and got.shape == (len(rows),) + v.shape[1:], (k, got.dtype, got.shape)
+        err = float(np.abs(got - v[rows]).max())
+        assert err < 1e-4, (k, err)
+
+
 @pytest.mark.gpu
 def test_bench_two_rank_code_path_on_one_gpu(gpu_device):
     """The N > 1 path of bench.py end to end -- `torch.distributed.run`, the shard plans of two ranks, the omegas gather of a strong-scaling
@@ -239,7 +281,7 @@ def test_bench_two_rank_code_path_on_one_gpu(gpu_device):
     env = dict(os.environ, HMMR_BENCH_BACKEND="gloo", HMMR_BENCH_ONE_DEVICE="1", HSA_ENABLE_IPC_MODE_LEGACY="0")
     r = subprocess.run([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1",
                         "--master-port", str(port), "bench.py", "--gpus", "2", "--video-frames", "512", "--steps", "2", "--warmup", "1",
-                        "--sustain", "0", "--dtype", "f16x3"], cwd=root, env=env, capture_output=True, text=True, timeout=900)
+                        "--sustain", "0", "--dtype", "f16x3", "--full"], cwd=root, env=env, capture_output=True, text=True, timeout=900)
     lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
     assert r.returncode == 0 and len(lines) == 1, (r.stdout[-500:], r.stderr[-1500:])
     js = json.loads(lines[0])
