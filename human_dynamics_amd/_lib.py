@@ -133,6 +133,23 @@ class SmplSource(C.Structure):
                 ("J_regressor", _fp), ("lbs_weights", _fp), ("kp_regressor", _fp), ("parents", _ip)]
 
 
+RENDER_MAX_FRAMES, RENDER_MIN_SIZE, RENDER_MAX_SIZE, RENDER_MAX_FACES = 4096, 16, 1024, 65536
+RENDER_BG_COLOR, RENDER_BG_FLOAT, RENDER_BG_FRAME = 0, 1, 2
+
+
+class RenderDesc(C.Structure):
+    """hmmr_render_desc_t: one call of the rasteriser (csrc/render.hip)"""
+    _fields_ = [("verts", _fp), ("ld_verts", C.c_int64), ("cams", _fp), ("ld_cam", C.c_int64), ("geom", _fp),
+                ("faces", _ip), ("face_colors", _fp), ("ld_face_colors", C.c_int64),
+                ("n", C.c_int), ("nv", C.c_int), ("nf", C.c_int), ("size", C.c_int),
+                ("rotate", C.c_int), ("rot", C.c_float * 9), ("color", C.c_float * 3), ("bg_color", C.c_float * 3),
+                ("light_dir", C.c_float * 3), ("light_int_ambient", C.c_float), ("light_int_directional", C.c_float),
+                ("light_color_ambient", C.c_float * 3), ("light_color_directional", C.c_float * 3),
+                ("bg_mode", C.c_int), ("bg_image", _vp), ("bg_add", C.c_float), ("bg_mul", C.c_float),
+                ("frame_h", C.c_int), ("frame_w", C.c_int), ("out_h", C.c_int), ("out_w", C.c_int),
+                ("rgb", _vp), ("alpha", _fp), ("face_index", _ip), ("ws", _vp), ("ws_bytes", C.c_size_t)]
+
+
 # name -> (restype, argtypes); mirrors include/hmmr_hip.h one to one
 SIGNATURES = {
     "hmmr_abi_version": (C.c_int, []),
@@ -177,6 +194,8 @@ SIGNATURES = {
     "hmmr_clock_probe": (C.c_int, [_vp, C.c_int, C.c_int, _vp, _vp]),
     "hmmr_render_handoff": (C.c_int, [_fp, C.c_int64, _fp, C.c_int64, _fp, C.c_int64, _fp, C.c_int, C.c_int, C.c_int,
                                       _fp, _fp, _fp, _vp]),
+    "hmmr_render_workspace_bytes": (C.c_size_t, [C.c_int, C.c_int, C.c_int]),
+    "hmmr_render_mesh": (C.c_int, [C.POINTER(RenderDesc), _vp]),
     "hmmr_eval_joints": (C.c_int, [_fp, _fp, C.c_int, C.c_int, C.c_int, C.c_int, _fp, _fp, _fp, _fp, _vp]),
     "hmmr_eval_verts": (C.c_int, [_fp, C.c_int64, _fp, C.c_int64, C.c_int, C.c_int, _fp, _vp]),
     "hmmr_global_rigid_transformation": (C.c_int, [_fp, _fp, _ip, C.c_int, _fp, _fp, C.c_int, _vp]),

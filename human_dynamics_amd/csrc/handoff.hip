@@ -15,27 +15,12 @@
 // contraction, so proj_verts is bit-identical to torch's `scale * (X + trans)`.
 #include "common.h"
 #include "hmmr_hip.h"
+#include "image_geom.h"
 
 namespace {
 
-struct FrameCam { float s, tx, ty; };
-
-// geom row = {undo_scale, start_x, start_y, proc_size, img_size}; geom == NULL: stay in the crop
-__device__ __forceinline__ FrameCam frame_camera(const float* cam, const float* g) {
-    FrameCam c = {cam[0], cam[1], cam[2]};
-    if (!g) return c;
-    const double undo = g[0], sx = g[1], sy = g[2], proc = g[3], size = g[4];
-    const double crop_s = proc * (double)cam[0] * 0.5;                 // camera in crop pixels
-    const double half = (2.0 / (double)cam[0]) * 0.5;
-    const double crop_tx = (double)cam[1] + half, crop_ty = (double)cam[2] + half;
-    const double orig_s = crop_s * undo;                               // camera in original pixels
-    const double orig_tx = crop_tx + (sx - proc) / crop_s, orig_ty = crop_ty + (sy - proc) / crop_s;
-    const double k = 2.0 / size;                                       // normalised original image
-    c.s = (float)(orig_s * k);
-    c.tx = (float)(orig_tx - 1.0 / (k * orig_s));
-    c.ty = (float)(orig_ty - 1.0 / (k * orig_s));
-    return c;
-}
+using hmmr_img::FrameCam;
+using hmmr_img::frame_camera;
 
 __global__ void render_handoff_kernel(const float* __restrict__ cams, long long ld_cam,
                                       const float* __restrict__ verts, long long ld_verts,

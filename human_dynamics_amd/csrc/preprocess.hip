@@ -9,19 +9,11 @@
 // HBM-bound: 3 B read (cached, ~4 taps) and 12 B written per output element.
 #include "common.h"
 #include "hmmr_hip.h"
+#include "image_geom.h"
 
 namespace {
 constexpr int S = 224;
-
-__device__ __forceinline__ void taps(int d, int src, int dst, int& s0, int& s1, double& w0, double& w1) {
-    float f = (float)(((double)d + 0.5) * ((double)src / (double)dst) - 0.5);
-    int s = (int)floorf(f);
-    f -= (float)s;
-    if (s < 0) { f = 0.f; s = 0; }
-    if (s >= src - 1) { f = 0.f; s = src - 1; }
-    s0 = s; s1 = min(s + 1, src - 1);
-    w0 = (double)(1.0f - f); w1 = (double)f;
-}
+using hmmr_img::taps;
 
 // geom[n] = {Hs, Ws, u0, v0}: scaled image size and the scaled-image coordinates of crop pixel (0,0)
 __global__ void crop_frames_kernel(const unsigned char* __restrict__ frames, const int4* __restrict__ geom,

@@ -1,0 +1,381 @@
+// Rasteriser for the demo views (include/hmmr_hip.h: hmmr_render_mesh).
+//
+// The reference draws each predicted mesh with neural_renderer (NMR) through VisRenderer
+// (src/util/render/nmr_renderer.py), one frame at a time.  Here n frames of one topology go through
+// three launches per slab of RENDER_CHUNK frames:
+//   1. render_prep_kernel    one workgroup per frame: the camera (and the optional change to the original
+//                            image), the optional rotation about the centroid, the projection of every
+//                            vertex, and the frame's subpixel bbox of the finite vertices;
+//   2. render_setup_kernel   one lane per (frame, face): the face's subpixel bbox, its barycentric and 1/z'
+//                            planes (fp64, rounded to fp32) and its shaded colour;
+//   3. render_raster_kernel  one workgroup per 64x64-subpixel tile of a frame (32x32 output pixels): the
+//                            frame's faces are streamed through LDS 256 at a time, culled by bbox against the
+//                            tile with an order-keeping ballot compaction, and tested against the lane's 16
+//                            subpixels held in registers; then the 2x2 pool, the composite and the stores.
+// Nothing is handed between workgroups inside a launch, there are no atomics, and every subpixel visits
+// the faces in index order, so the result is bit-reproducible and a frame renders the same alone or in a batch.
+// Every face is tested by every tile its bbox overlaps: no fixed-capacity bin can overflow.
+#include "common.h"
+#include "hmmr_hip.h"
+#include "image_geom.h"
+
+namespace {
+
+constexpr int RENDER_CHUNK = 64;          // frames per launch triple (bounds the workspace)
+constexpr int TILE = 64;                  // subpixels per tile side
+constexpr int THREADS = 256;
+constexpr float EYE_Z = 2.7320508075688772f;   // 1 / tan(30 deg) + 1: look_at eye at (0, 0, -EYE_Z)
+
+struct FaceRec {                          // barycentrics w_i = A_i (u - qx0) + B_i (v - qy0) + [i == 0]
+    float qx0, qy0, a0, b0, a1, b1, a2, b2, az, bz, iz0, pad;   // 1/z' = iz0 + az (u - qx0) + bz (v - qy0)
+};
+
+struct Ws {                               // carve-up of the caller's workspace for one slab of frames
+    float4* pv;                           // [CH][nv] projected vertex {p.x, p.y, z, 0}
+    int4* fbox;                           // [CH] frame bbox {c0, c1, r0, r1} in subpixels
+    int2* bbox;                           // [CH][nf] {c0 | c1 << 16, r0 | r1 << 16}
+    FaceRec* rec;                         // [CH][nf]
+    float4* col;                          // [CH][nf] shaded colour
+};
+
+__host__ __device__ inline size_t align256(size_t x) { return (x + 255) & ~(size_t)255; }
+
+__host__ __device__ inline Ws carve(void* base, int ch, int nv, int nf) {
+    char* p = (char*)base;
+    Ws w;
+    w.pv = (float4*)p;  p += align256((size_t)ch * nv * sizeof(float4));
+    w.fbox = (int4*)p;  p += align256((size_t)ch * sizeof(int4));
+    w.bbox = (int2*)p;  p += align256((size_t)ch * nf * sizeof(int2));
+    w.rec = (FaceRec*)p; p += align256((size_t)ch * nf * sizeof(FaceRec));
+    w.col = (float4*)p;
+    return w;
+}
+
+inline size_t ws_bytes(int ch, int nv, int nf) {
+    return align256((size_t)ch * nv * sizeof(float4)) + align256((size_t)ch * sizeof(int4)) +
+           align256((size_t)ch * nf * sizeof(int2)) + align256((size_t)ch * nf * sizeof(FaceRec)) +
+           align256((size_t)ch * nf * sizeof(float4));
+}
+
+// subpixel index range whose centres (i + 0.5) / S - 1 may lie in [lo, hi] (ndc), widened by one subpixel so that the
+// fp32 edge tests decide at the border; clamped to [0, 2S-1] (empty: first > last)
+__device__ inline void sub_range(double lo, double hi, int S, int& a, int& b) {
+    const double fa = floor(lo * S + S - 0.5) , fb = ceil(hi * S + S - 0.5);
+    a = fa < 0.0 ? 0 : (fa > 2.0 * S ? 2 * S : (int)fa);
+    b = fb > 2.0 * S - 1 ? 2 * S - 1 : (fb < -1.0 ? -1 : (int)fb);
+}
+
+__device__ inline bool finite3(float4 p) { return isfinite(p.x) && isfinite(p.y) && isfinite(p.z); }
+
+// ---- 1. per frame: camera, rotation, projection, frame bbox ------------------------------------------------------
+__global__ void __launch_bounds__(THREADS) render_prep_kernel(hmmr_render_desc_t d, int f0, Ws w) {
+    const int fl = blockIdx.x, f = f0 + fl, t = threadIdx.x;
+    const hmmr_img::FrameCam c = hmmr_img::frame_camera(d.cams + (long long)f * d.ld_cam,
+                                                        d.geom ? d.geom + (long long)f * 5 : nullptr);
+    const float* v = d.verts + (long long)f * d.ld_verts;
+    __shared__ float red[3][THREADS];
+    __shared__ float mn[4][THREADS];
+    float cx = 0.f, cy = 0.f, cz = 0.f;
+    if (d.rotate) {
+        float sx = 0.f, sy = 0.f, sz = 0.f;
+        for (int i = t; i < d.nv; i += THREADS) { sx += v[3 * i]; sy += v[3 * i + 1]; sz += v[3 * i + 2]; }
+        red[0][t] = sx; red[1][t] = sy; red[2][t] = sz;
+        __syncthreads();
+        for (int o = THREADS / 2; o > 0; o >>= 1) {
+            if (t < o) { red[0][t] += red[0][t + o]; red[1][t] += red[1][t + o]; red[2][t] += red[2][t + o]; }
+            __syncthreads();
+        }
+        cx = red[0][0] / (float)d.nv; cy = red[1][0] / (float)d.nv; cz = red[2][0] / (float)d.nv;
+    }
+    float xlo = INFINITY, xhi = -INFINITY, ylo = INFINITY, yhi = -INFINITY;
+    for (int i = t; i < d.nv; i += THREADS) {
+        float x = v[3 * i], y = v[3 * i + 1], z = v[3 * i + 2];
+        if (d.rotate) {
+            const float ax = x - cx, ay = y - cy, az = z - cz;
+            const float* R = d.rot;
+            x = __fadd_rn(__fadd_rn(__fadd_rn(__fmul_rn(R[0], ax), __fmul_rn(R[1], ay)), __fmul_rn(R[2], az)), cx);
+            y = __fadd_rn(__fadd_rn(__fadd_rn(__fmul_rn(R[3], ax), __fmul_rn(R[4], ay)), __fmul_rn(R[5], az)), cy);
+            z = __fadd_rn(__fadd_rn(__fadd_rn(__fmul_rn(R[6], ax), __fmul_rn(R[7], ay)), __fmul_rn(R[8], az)), cz);
+        }
+        float4 p;
+        p.x = __fmul_rn(c.s, __fadd_rn(x, c.tx));
+        p.y = -__fmul_rn(c.s, __fadd_rn(y, c.ty));                    // image y points down
+        p.z = z;
+        p.w = 0.f;
+        w.pv[(long long)fl * d.nv + i] = p;
+        if (finite3(p)) { xlo = fminf(xlo, p.x); xhi = fmaxf(xhi, p.x); ylo = fminf(ylo, -p.y); yhi = fmaxf(yhi, -p.y); }
+    }
+    mn[0][t] = xlo; mn[1][t] = -xhi; mn[2][t] = ylo; mn[3][t] = -yhi;
+    __syncthreads();
+    for (int o = THREADS / 2; o > 0; o >>= 1) {
+        if (t < o)
+            for (int k = 0; k < 4; ++k) mn[k][t] = fminf(mn[k][t], mn[k][t + o]);
+        __syncthreads();
+    }
+    if (t == 0) {
+        int4 b;
+        if (mn[0][0] <= -mn[1][0]) {
+            sub_range(mn[0][0], -mn[1][0], d.size, b.x, b.y);
+            sub_range(mn[2][0], -mn[3][0], d.size, b.z, b.w);
+        } else {
+            b = make_int4(1, 0, 1, 0);
+        }
+        w.fbox[fl] = b;
+    }
+}
+
+// ---- 2. per (frame, face): bbox, planes, shading -----------------------------------------------------------------
+__global__ void __launch_bounds__(THREADS) render_setup_kernel(hmmr_render_desc_t d, int f0, Ws w) {
+    const int fl = blockIdx.y, f = f0 + fl;
+    const int j = blockIdx.x * THREADS + threadIdx.x;
+    if (j >= d.nf) return;
+    const long long o = (long long)fl * d.nf + j;
+    const int* fi = d.faces + 3LL * j;
+    const float4* pv = w.pv + (long long)fl * d.nv;
+    const float4 p0 = pv[fi[0]], p1 = pv[fi[1]], p2 = pv[fi[2]];
+    int2 bb = make_int2(1, 1);                                         // empty: c0 = 1 > c1 = 0
+    FaceRec r = {};
+    float4 col = make_float4(0.f, 0.f, 0.f, 0.f);
+    // the triangle in the unflipped camera: q = (p.x, -p.y); z' = z + EYE_Z in fp32 (look_at is a pure translation)
+    const double qx[3] = {p0.x, p1.x, p2.x}, qy[3] = {-p0.y, -p1.y, -p2.y};
+    const double zp[3] = {(double)(p0.z + EYE_Z), (double)(p1.z + EYE_Z), (double)(p2.z + EYE_Z)};
+    const double area2 = (qx[1] - qx[0]) * (qy[2] - qy[0]) - (qy[1] - qy[0]) * (qx[2] - qx[0]);
+    if (finite3(p0) && finite3(p1) && finite3(p2) && area2 != 0.0 && isfinite(area2)) {
+        double A[3], B[3];
+        for (int i = 0; i < 3; ++i) {
+            const int a = (i + 1) % 3, b = (i + 2) % 3;
+            A[i] = (qy[a] - qy[b]) / area2;
+            B[i] = (qx[b] - qx[a]) / area2;
+        }
+        const double iz[3] = {1.0 / zp[0], 1.0 / zp[1], 1.0 / zp[2]};
+        r.qx0 = p0.x; r.qy0 = -p0.y;
+        r.a0 = (float)A[0]; r.b0 = (float)B[0]; r.a1 = (float)A[1]; r.b1 = (float)B[1]; r.a2 = (float)A[2]; r.b2 = (float)B[2];
+        r.az = (float)(A[0] * iz[0] + A[1] * iz[1] + A[2] * iz[2]);
+        r.bz = (float)(B[0] * iz[0] + B[1] * iz[1] + B[2] * iz[2]);
+        r.iz0 = (float)iz[0];
+        int c0, c1, r0, r1;
+        sub_range(fmin(qx[0], fmin(qx[1], qx[2])), fmax(qx[0], fmax(qx[1], qx[2])), d.size, c0, c1);
+        sub_range(fmin(qy[0], fmin(qy[1], qy[2])), fmax(qy[0], fmax(qy[1], qy[2])), d.size, r0, r1);
+        if (c0 <= c1 && r0 <= r1) bb = make_int2(c0 | (c1 << 16), r0 | (r1 << 16));
+        // shading with the viewer-facing unit normal of the projected (y-flipped) triangle, before the z shift
+        const float e0x = p0.x - p1.x, e0y = p0.y - p1.y, e0z = p0.z - p1.z;
+        const float e2x = p2.x - p1.x, e2y = p2.y - p1.y, e2z = p2.z - p1.z;
+        float nx = e0y * e2z - e0z * e2y, ny = e0z * e2x - e0x * e2z, nz = e0x * e2y - e0y * e2x;
+        if (nz > 0.f) { nx = -nx; ny = -ny; nz = -nz; }
+        const float inv = 1.f / fmaxf(sqrtf(nx * nx + ny * ny + nz * nz), 1e-5f);
+        const float cosv = fmaxf(0.f, (nx * d.light_dir[0] + ny * d.light_dir[1] + nz * d.light_dir[2]) * inv);
+        float tex[3] = {d.color[0], d.color[1], d.color[2]};
+        if (d.face_colors) {
+            const float* fc = d.face_colors + (long long)f * d.ld_face_colors + 3LL * j;
+            tex[0] = fc[0]; tex[1] = fc[1]; tex[2] = fc[2];
+        }
+        float lc[3];
+#pragma unroll
+        for (int k = 0; k < 3; ++k)
+            lc[k] = tex[k] * (d.light_int_ambient * d.light_color_ambient[k] +
+                              d.light_int_directional * d.light_color_directional[k] * cosv);
+        col = make_float4(lc[0], lc[1], lc[2], 0.f);
+    }
+    w.bbox[o] = bb;
+    w.rec[o] = r;
+    w.col[o] = col;
+}
+
+// ---- 3. per (frame, tile): raster, pool, composite ---------------------------------------------------------------
+// lane layout: wave wv owns subpixel rows [16 wv, 16 wv + 16) of the tile; lane l owns subpixel columns 2 (l & 31) + {0, 1}
+// and rows 16 wv + 8 (l >> 5) + [0, 8), i.e. output pixels (l & 31, 8 wv + 4 (l >> 5) + [0, 4)): the pool is lane-local
+__global__ void __launch_bounds__(THREADS) render_raster_kernel(hmmr_render_desc_t d, int f0, Ws w, int tiles_x) {
+    const int fl = blockIdx.y, f = f0 + fl, t = threadIdx.x;
+    const int tx = blockIdx.x % tiles_x, ty = blockIdx.x / tiles_x;
+    const int S = d.size, S2 = 2 * S;
+    const int TC = tx * TILE, TR = ty * TILE;
+    if (!d.face_index && (TC / 2 >= d.out_w || TR / 2 >= d.out_h)) return;   // removed by remove_pads
+
+    __shared__ FaceRec s_rec[THREADS];
+    __shared__ int2 s_bb[THREADS];
+    __shared__ int s_id[THREADS];
+    __shared__ int s_cnt[THREADS / HMMR_WAVE];
+    __shared__ double s_lut[256];
+
+    const int wv = t / HMMR_WAVE, l = t % HMMR_WAVE;
+    const int px = l & 31, g = l >> 5;
+    const int col0 = TC + 2 * px;                       // the lane's subpixel columns col0, col0 + 1
+    const int row0 = TR + 16 * wv + 8 * g;              // the lane's subpixel rows row0 .. row0 + 7
+    const int band_lo = TR + 16 * wv, band_hi = band_lo + 15;
+    float uc[2], vr[8];
+    for (int k = 0; k < 2; ++k) uc[k] = (float)(2 * (col0 + k) + 1 - S2) / (float)S2;
+    for (int k = 0; k < 8; ++k) vr[k] = (float)(2 * (row0 + k) + 1 - S2) / (float)S2;
+
+    float best[8][2];
+    int bid[8][2];
+#pragma unroll
+    for (int a = 0; a < 8; ++a)
+#pragma unroll
+        for (int b = 0; b < 2; ++b) { best[a][b] = -1.f; bid[a][b] = -1; }
+
+    const int4 fb = w.fbox[fl];
+    const bool any = !(fb.y < TC || fb.x > TC + TILE - 1 || fb.w < TR || fb.z > TR + TILE - 1);
+    if (any) {
+        const int2* bbox = w.bbox + (long long)fl * d.nf;
+        const FaceRec* rec = w.rec + (long long)fl * d.nf;
+        for (int base = 0; base < d.nf; base += THREADS) {
+            const int j = base + t;
+            bool ok = false;
+            int2 bb = make_int2(1, 0);
+            if (j < d.nf) {
+                bb = bbox[j];
+                const int c0 = bb.x & 0xffff, c1 = bb.x >> 16, r0 = bb.y & 0xffff, r1 = bb.y >> 16;
+                ok = c0 <= c1 && !(c1 < TC || c0 > TC + TILE - 1 || r1 < TR || r0 > TR + TILE - 1);
+            }
+            // order-keeping compaction: rank within the wave by ballot, waves in order through LDS
+            const unsigned long long m = __ballot(ok);
+            const int rank = __popcll(m & ((1ull << l) - 1ull));
+            if (l == 0) s_cnt[wv] = __popcll(m);
+            __syncthreads();
+            int off = 0, total = 0;
+            for (int k = 0; k < THREADS / HMMR_WAVE; ++k) { off += k < wv ? s_cnt[k] : 0; total += s_cnt[k]; }
+            if (ok) { s_rec[off + rank] = rec[j]; s_bb[off + rank] = bb; s_id[off + rank] = j; }
+            __syncthreads();
+            for (int i = 0; i < total; ++i) {
+                const int2 b = s_bb[i];
+                const int r0 = b.y & 0xffff, r1 = b.y >> 16;
+                if (r1 < band_lo || r0 > band_hi) continue;                 // the same for the whole wave
+                const int c0 = b.x & 0xffff, c1 = b.x >> 16;
+                if (c1 < col0 || c0 > col0 + 1 || r1 < row0 || r0 > row0 + 7) continue;
+                const FaceRec q = s_rec[i];
+                const int id = s_id[i];
+                float t0[2], t1[2], t2[2], tz[2];
+#pragma unroll
+                for (int k = 0; k < 2; ++k) {
+                    const float du = uc[k] - q.qx0;
+                    t0[k] = fmaf(q.a0, du, 1.f); t1[k] = q.a1 * du; t2[k] = q.a2 * du; tz[k] = fmaf(q.az, du, q.iz0);
+                }
+#pragma unroll
+                for (int a = 0; a < 8; ++a) {
+                    const float dv = vr[a] - q.qy0;
+#pragma unroll
+                    for (int k = 0; k < 2; ++k) {
+                        const float w0 = fmaf(q.b0, dv, t0[k]), w1 = fmaf(q.b1, dv, t1[k]), w2 = fmaf(q.b2, dv, t2[k]);
+                        const float iz = fmaf(q.bz, dv, tz[k]);
+                        // z' in [0.1, 100] <=> 1/z' in [0.01, 10]; strictly nearer replaces: ties keep the lower index
+                        if (w0 >= 0.f && w1 >= 0.f && w2 >= 0.f && iz >= 0.01f && iz <= 10.f && iz > best[a][k]) {
+                            best[a][k] = iz;
+                            bid[a][k] = id;
+                        }
+                    }
+                }
+            }
+            __syncthreads();
+        }
+    }
+
+    if (d.face_index) {
+        int32_t* fim = d.face_index + (long long)f * S2 * S2;
+        if (col0 < S2)
+#pragma unroll
+            for (int a = 0; a < 8; ++a)
+                if (row0 + a < S2) *(int2*)(fim + (long long)(row0 + a) * S2 + col0) = make_int2(bid[a][0], bid[a][1]);
+    }
+
+    if (d.bg_mode == HMMR_RENDER_BG_FRAME) {
+        s_lut[t] = ((double)t / 255.0 - 0.5) * 2.0;                   // ((img / 255.) - 0.5) * 2 (run_video.py)
+        __syncthreads();
+    }
+    const int X = TC / 2 + px;
+    if (X >= d.out_w) return;
+    const float4* col = w.col + (long long)fl * d.nf;
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+        const int Y = (row0 >> 1) + k;
+        if (Y >= d.out_h) break;
+        float sum[3] = {0.f, 0.f, 0.f};
+        int cov = 0;
+        float sub[4][3];
+#pragma unroll
+        for (int s = 0; s < 4; ++s) {
+            const int id = bid[2 * k + (s >> 1)][s & 1];
+            if (id >= 0) {
+                const float4 c = col[id];
+                sub[s][0] = c.x; sub[s][1] = c.y; sub[s][2] = c.z;
+                ++cov;
+            } else {
+                sub[s][0] = d.bg_color[0]; sub[s][1] = d.bg_color[1]; sub[s][2] = d.bg_color[2];
+            }
+        }
+        for (int ch = 0; ch < 3; ++ch) sum[ch] = ((sub[0][ch] + sub[1][ch]) + (sub[2][ch] + sub[3][ch])) * 0.25f;
+        const float al = (float)cov * 0.25f, om = 1.f - al;
+        const long long pix = ((long long)f * d.out_h + Y) * d.out_w + X;
+        unsigned char o[3];
+        if (d.bg_mode == HMMR_RENDER_BG_FRAME) {
+            int x0, x1, y0, y1; double a0, a1, b0, b1;
+            hmmr_img::taps(X, d.frame_w, d.out_w, x0, x1, a0, a1);
+            hmmr_img::taps(Y, d.frame_h, d.out_h, y0, y1, b0, b1);
+            const unsigned char* fr = (const unsigned char*)d.bg_image + (long long)f * d.frame_h * d.frame_w * 3;
+            for (int ch = 0; ch < 3; ++ch) {
+                auto pxl = [&](int yy, int xx) { return s_lut[fr[((long long)yy * d.frame_w + xx) * 3 + ch]]; };
+                const double img = ((pxl(y0, x0) * a0 + pxl(y0, x1) * a1) * b0 + (pxl(y1, x0) * a0 + pxl(y1, x1) * a1) * b1);
+                const double bg = ((img + 1.0) * 0.5) * 255.0;
+                const float rend = fminf(fmaxf(sum[ch], 0.f), 1.f) * 255.f;
+                const double v = bg * (double)om + (double)(rend * al);
+                o[ch] = (unsigned char)(int)v;
+            }
+        } else if (d.bg_mode == HMMR_RENDER_BG_FLOAT) {
+            const float* im = (const float*)d.bg_image + (((long long)f * S + Y) * S + X) * 3;
+            for (int ch = 0; ch < 3; ++ch) {
+                const float bg = (im[ch] + d.bg_add) * d.bg_mul;
+                const float rend = fminf(fmaxf(sum[ch], 0.f), 1.f) * 255.f;
+                o[ch] = (unsigned char)(int)(bg * om + rend * al);
+            }
+        } else {
+            for (int ch = 0; ch < 3; ++ch) o[ch] = (unsigned char)(int)(fminf(fmaxf(sum[ch], 0.f), 1.f) * 255.f);
+        }
+        unsigned char* out = d.rgb + pix * 3;
+        out[0] = o[0]; out[1] = o[1]; out[2] = o[2];
+        if (d.alpha) d.alpha[pix] = al;
+    }
+}
+
+}  // namespace
+
+extern "C" size_t hmmr_render_workspace_bytes(int n, int nv, int nf) {
+    if (n <= 0 || n > HMMR_RENDER_MAX_FRAMES || nv <= 0 || nf <= 0 || nf > HMMR_RENDER_MAX_FACES) return 0;
+    return ws_bytes(n < RENDER_CHUNK ? n : RENDER_CHUNK, nv, nf);
+}
+
+extern "C" int hmmr_render_mesh(const hmmr_render_desc_t* d, void* stream) {
+    HMMR_REQUIRE(d, "hmmr_render_mesh: NULL descriptor");
+    HMMR_REQUIRE(d->verts && d->cams && d->faces && d->rgb && d->ws, "hmmr_render_mesh: NULL operand");
+    HMMR_REQUIRE(d->n >= 1 && d->n <= HMMR_RENDER_MAX_FRAMES, "hmmr_render_mesh: n = %d outside [1, %d]", d->n,
+                 HMMR_RENDER_MAX_FRAMES);
+    HMMR_REQUIRE(d->size >= HMMR_RENDER_MIN_SIZE && d->size <= HMMR_RENDER_MAX_SIZE,
+                 "hmmr_render_mesh: size = %d outside [%d, %d]", d->size, HMMR_RENDER_MIN_SIZE, HMMR_RENDER_MAX_SIZE);
+    HMMR_REQUIRE(d->nf >= 1 && d->nf <= HMMR_RENDER_MAX_FACES, "hmmr_render_mesh: nf = %d outside [1, %d]", d->nf,
+                 HMMR_RENDER_MAX_FACES);
+    HMMR_REQUIRE(d->nv >= 3, "hmmr_render_mesh: nv = %d < 3", d->nv);
+    HMMR_REQUIRE(d->ld_verts >= 3LL * d->nv && d->ld_cam >= 3, "hmmr_render_mesh: row strides smaller than the rows");
+    HMMR_REQUIRE(!d->face_colors || d->ld_face_colors == 0 || d->ld_face_colors >= 3LL * d->nf,
+                 "hmmr_render_mesh: face_colors row stride smaller than the rows");
+    HMMR_REQUIRE(d->out_h >= 1 && d->out_w >= 1 && d->out_h <= d->size && d->out_w <= d->size,
+                 "hmmr_render_mesh: output %d x %d outside [1, size = %d]", d->out_h, d->out_w, d->size);
+    HMMR_REQUIRE(d->bg_mode >= HMMR_RENDER_BG_COLOR && d->bg_mode <= HMMR_RENDER_BG_FRAME, "hmmr_render_mesh: bad bg_mode %d",
+                 d->bg_mode);
+    HMMR_REQUIRE(d->bg_mode == HMMR_RENDER_BG_COLOR || d->bg_image, "hmmr_render_mesh: bg_mode %d without bg_image", d->bg_mode);
+    HMMR_REQUIRE(d->bg_mode != HMMR_RENDER_BG_FRAME || (d->frame_h >= 1 && d->frame_w >= 1),
+                 "hmmr_render_mesh: bad frame size %d x %d", d->frame_h, d->frame_w);
+    const size_t need = hmmr_render_workspace_bytes(d->n, d->nv, d->nf);
+    HMMR_REQUIRE(d->ws_bytes >= need, "hmmr_render_mesh: workspace %zu bytes < %zu", d->ws_bytes, need);
+    const int ch = d->n < RENDER_CHUNK ? d->n : RENDER_CHUNK;
+    const Ws w = carve(d->ws, ch, d->nv, d->nf);
+    const int tiles_x = (2 * d->size + TILE - 1) / TILE;
+    hipStream_t st = (hipStream_t)stream;
+    for (int f0 = 0; f0 < d->n; f0 += RENDER_CHUNK) {
+        const int m = d->n - f0 < RENDER_CHUNK ? d->n - f0 : RENDER_CHUNK;
+        hipLaunchKernelGGL(render_prep_kernel, dim3(m), dim3(THREADS), 0, st, *d, f0, w);
+        HMMR_CHECK_HIP(hipGetLastError());
+        hipLaunchKernelGGL(render_setup_kernel, dim3((d->nf + THREADS - 1) / THREADS, m), dim3(THREADS), 0, st, *d, f0, w);
+        HMMR_CHECK_HIP(hipGetLastError());
+        hipLaunchKernelGGL(render_raster_kernel, dim3(tiles_x * tiles_x, m), dim3(THREADS), 0, st, *d, f0, w, tiles_x);
+        HMMR_CHECK_HIP(hipGetLastError());
+    }
+    return 0;
+}

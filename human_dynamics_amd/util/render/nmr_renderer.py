@@ -1,0 +1,152 @@
+"""VisRenderer: a drop-in for the reference's class of the same name (src/util/render/nmr_renderer.py:43-240) on the
+project's own rasteriser (csrc/render.hip) instead of neural_renderer, which does not exist for ROCm.
+
+The reference's `visualize_img`, `visualize_img_orig` and `render_preds` run unchanged on top of it for their mesh
+panels (they set `.renderer.image_size` and call `__call__` / `rotated`); their skeleton and text drawing, the collage
+and the PNG / video writing need cv2 and stay with the caller.  Inputs may be numpy arrays or device tensors; results
+are what the reference returns (uint8 numpy: [S,S,3], [B,S,S,3], RGBA [S,S,4], or the silhouette), or the same data as
+device tensors with `on_device=True`.  Only t_size = 1 textures (one colour per face) are supported.
+"""
+from __future__ import annotations
+
+import numpy as np
+import torch
+
+from ... import _lib as L
+from ...tf_smpl.batch_smpl import _SmplUnpickler
+from .raster import COLORS, MeshFaces, render_mesh, rodrigues
+
+colors = COLORS
+
+
+def load_faces(face_path):
+    """Faces [F,3] int32 from a .npy (the reference's smpl_faces.npy) or from an SMPL .pkl's `f` (read without
+    chumpy, as batch_smpl.load_smpl_constants reads the model)."""
+    if str(face_path).endswith(".pkl"):
+        with open(face_path, "rb") as fh:
+            dd = _SmplUnpickler(fh, encoding="latin1").load()
+        f = dd["f"]
+        f = getattr(f, "r", f)
+    else:
+        f = np.load(face_path)
+    return np.asarray(f).astype(np.int32)
+
+
+class _RendererState(object):
+    """The attributes of nr.Renderer that VisRenderer and visualize_img_orig read or set."""
+
+    def __init__(self, image_size):
+        self.image_size = image_size
+        self.light_direction = [0, 1, 0]
+        self.light_intensity_directional = 0.5
+        self.light_intensity_ambient = 0.5
+        self.light_color_ambient = [1, 1, 1]
+        self.light_color_directional = [1, 1, 1]
+        self.background_color = [0, 0, 0]
+        self.camera_mode, self.perspective, self.viewing_angle = 'look_at', False, 30
+        self.near, self.far, self.anti_aliasing, self.fill_back = 0.1, 100, True, True
+
+
+def _dims(x):
+    return x.dim() if isinstance(x, torch.Tensor) else np.ndim(x)
+
+
+class VisRenderer(object):
+    """Renders meshes with the same orthographic projection as HMR (no perspective); faces F x 3 or 1 x F x 3."""
+
+    def __init__(self, img_size=256, face_path='src/tf_smpl/smpl_faces.npy', t_size=1, device="cuda", on_device=False,
+                 faces=None):
+        if t_size != 1:
+            raise NotImplementedError("VisRenderer: textures with t_size > 1 are not supported (one colour per face)")
+        self.renderer = _RendererState(img_size)
+        self.set_light_dir([1, .5, -1], int_dir=0.3, int_amb=0.7)
+        self.set_bgcolor([1, 1, 1.])
+        self.img_size = img_size
+        self.faces_np = np.asarray(faces if faces is not None else load_faces(face_path)).astype(np.int32)
+        if self.faces_np.ndim == 3:
+            self.faces_np = self.faces_np[0]
+        self._faces = MeshFaces(self.faces_np)
+        self.device = torch.device(device)
+        self.on_device = on_device
+        self.default_cam = np.array([[0.9, 0, 0]], np.float32)
+
+    def _tensor(self, x):
+        if isinstance(x, torch.Tensor):
+            return x.to(self.device, torch.float32)
+        return torch.as_tensor(np.asarray(x, np.float32), device=self.device)
+
+    def _render(self, verts, cam, texture, rend_mask, alpha, img, color_name, rot):
+        num_batch = 1
+        if _dims(verts) == 3 and verts.shape[0] != 1:
+            num_batch = verts.shape[0]
+            if cam is not None:
+                assert _dims(cam) == 2 and cam.shape[0] == num_batch
+            if img is not None:
+                assert img.ndim == 4 and img.shape[0] == num_batch
+        v = self._tensor(verts)
+        if v.dim() == 2:
+            v = v.unsqueeze(0)
+        n = v.shape[0]
+        c = self._tensor(self.default_cam if cam is None else cam).reshape(-1, 3)
+        if c.shape[0] == 1 and n > 1:
+            c = c.expand(n, 3).contiguous()
+        face_colors = None
+        if texture is not None:
+            t = self._tensor(texture)
+            if t.dim() == 5:
+                t = t.unsqueeze(0)
+            face_colors = t.reshape(t.shape[0], t.shape[1], -1, 3)[:, :, 0, :]      # t_size = 1: one colour per face
+            if face_colors.shape[0] == 1:
+                face_colors = face_colors[0]
+        r = self.renderer
+        S = int(r.image_size)
+        kw = dict(color=colors[color_name], face_colors=face_colors, bg_color=r.background_color,
+                  light_dir=r.light_direction, int_dir=r.light_intensity_directional,
+                  int_amb=r.light_intensity_ambient, col_dir=r.light_color_directional, col_amb=r.light_color_ambient,
+                  rot=rot)
+        if img is not None and not rend_mask:
+            im = self._tensor(img).reshape(n, S, S, 3)
+            out = render_mesh(v, c, self._faces, S, bg_mode=L.RENDER_BG_FLOAT, bg_image=im, **kw)["rgb"]
+            if num_batch == 1:
+                out = out[0]
+            return out if self.on_device else out.cpu().numpy()
+        res = render_mesh(v, c, self._faces, S, want_alpha=rend_mask or alpha, **kw)
+        if rend_mask:                          # render_silhouettes, repeated to 3 channels as the reference does
+            sil = (torch.clamp(res["alpha"], 0, 1) * 255.0).to(torch.uint8)        # [n,S,S]
+            out = sil.permute(1, 2, 0).repeat(1, 1, 3).unsqueeze(0)                # [1,S,S,3n]
+            if num_batch == 1:
+                out = out[0]
+        elif alpha:
+            a = (res["alpha"] * 255).to(torch.uint8)
+            out = torch.cat([res["rgb"], a.unsqueeze(-1)], -1)
+            if num_batch == 1:
+                out = out[0]
+        else:
+            out = res["rgb"][0] if num_batch == 1 else res["rgb"]
+        return out if self.on_device else out.cpu().numpy()
+
+    def __call__(self, verts, cam=None, texture=None, rend_mask=False, alpha=False, img=None, color_name='blue'):
+        """verts [V,3] or [B,V,3], cam [3] or [B,3] ([s, tx, ty], HMR's), img [S,S,3] / [B,S,S,3] in [0, 255]:
+        uint8 [S,S,3] (or [B,S,S,3]); RGBA [S,S,4] with alpha; the silhouette with rend_mask."""
+        return self._render(verts, cam, texture, rend_mask, alpha, img, color_name, None)
+
+    def rotated(self, verts, deg, axis='y', cam=None, texture=None, rend_mask=False, alpha=False, color_name='blue'):
+        """The mesh rotated by `deg` about `axis` through its centroid, then rendered as __call__ does (no image)."""
+        v = verts if _dims(verts) == 3 else verts[None]
+        return self._render(v, cam, texture, rend_mask, alpha, None, color_name, rodrigues(deg, axis))
+
+    def make_alpha(self, rend, mask):
+        rend = rend.astype(np.uint8)
+        alpha = (mask * 255).astype(np.uint8)
+        return np.dstack((rend, alpha))
+
+    def set_light_dir(self, direction, int_dir=0.8, int_amb=0.8):
+        self.renderer.light_direction = direction
+        self.renderer.light_intensity_directional = int_dir
+        self.renderer.light_intensity_ambient = int_amb
+
+    def set_bgcolor(self, color):
+        self.renderer.background_color = color
+
+
+__all__ = ["VisRenderer", "colors", "load_faces"]

@@ -1,0 +1,73 @@
+"""The three mesh panels of the demo's `render_preds` (src/evaluation/run_video.py:110-202) for all n frames at once:
+
+    render_og  visualize_img_orig's mesh over the original frame (down-scaled to max_img_size, make_square, remove_pads)
+    rot_og     the same camera, the mesh rotated 90 deg about y through its centroid, on white (VisRenderer.rotated)
+    rend_crop  visualize_img's mesh over the 224x224 crop
+
+Each panel is one hmmr_render_mesh call (three launches per 64 frames) reading cams / verts in place inside the packed
+per-frame records; the camera change to the original image is the device code of hmmr_render_handoff, so nothing
+crosses PCIe until the caller downloads the uint8 panels.  The skeleton panel, draw_text, the 2x2 collage and the PNG /
+mp4 writing need cv2 and ffmpeg and are left to the caller.
+"""
+from __future__ import annotations
+
+import numpy as np
+import torch
+
+from ... import _lib as L
+from .handoff import orig_image_geometry
+from .raster import COLORS, MeshFaces, render_mesh, rodrigues
+
+
+def orig_output_size(frame_hw, max_img_size=720):
+    """(h', w', S): the frame after visualize_img_orig's optional down-scale (resize_img's floor) and the square side."""
+    h, w = int(frame_hw[0]), int(frame_hw[1])
+    if max(h, w) > max_img_size:
+        s = max_img_size / float(max(h, w))
+        h, w = int(np.floor(h * s)), int(np.floor(w * s))
+    return h, w, max(h, w)
+
+
+def _cams_verts(records, layout, device):
+    if isinstance(records, dict):                      # Tester.predict_all_images' dict (host or device)
+        cams = torch.as_tensor(np.asarray(records["cams"], np.float32) if not torch.is_tensor(records["cams"])
+                               else records["cams"], device=device).float()
+        verts = torch.as_tensor(np.asarray(records["verts"], np.float32) if not torch.is_tensor(records["verts"])
+                                else records["verts"], device=device).float()
+        return cams.reshape(cams.shape[0], -1), verts
+    get = {k: (off, size, shp) for k, shp, off, size in layout}
+    oc, sc, _ = get["cams"]
+    ov, sv, shp_v = get["verts"]
+    return records[:, oc:oc + sc], records[:, ov:ov + sv].unflatten(1, tuple(shp_v))
+
+
+def render_views(records, layout, frames_uint8, image_og_params, faces, crops=None, views=('orig', 'rotated', 'crop'),
+                 max_img_size=720, mesh_color='blue', device=None):
+    """records [n, rec_len] packed per-frame records (Tester.predict_records, dist.record_layout) or the dict of
+    predict_all_images; frames_uint8 [n,H,W,3] original frames; image_og_params: n dicts of process_image (start_pt,
+    scale, im_shape); faces [F,3] (or a MeshFaces); crops [n,224,224,3] in [-1, 1] for the crop panel.
+    -> {'orig': uint8 [n,h',w',3], 'rotated': uint8 [n,h',w',3], 'crop': uint8 [n,224,224,3]} on the device."""
+    if device is None:
+        device = records.device if torch.is_tensor(records) else torch.device("cuda", torch.cuda.current_device())
+    faces = faces if isinstance(faces, MeshFaces) else MeshFaces(faces)
+    cams, verts = _cams_verts(records, layout, device)
+    n = verts.shape[0]
+    color = COLORS[mesh_color]
+    out = {}
+    if 'orig' in views or 'rotated' in views:
+        h, w, S = orig_output_size(frames_uint8.shape[1:3], max_img_size)
+        geom = np.stack([orig_image_geometry(image_og_params[i], frames_uint8.shape[1:3], max_img_size) for i in range(n)])
+        if 'orig' in views:
+            fr = frames_uint8 if torch.is_tensor(frames_uint8) else torch.from_numpy(np.ascontiguousarray(frames_uint8))
+            out['orig'] = render_mesh(verts, cams, faces, S, geom=geom, color=color, bg_mode=L.RENDER_BG_FRAME,
+                                      bg_image=fr.to(device), out_hw=(h, w))["rgb"]
+        if 'rotated' in views:
+            out['rotated'] = render_mesh(verts, cams, faces, S, geom=geom, rot=rodrigues(90, 'y'), color=color,
+                                         out_hw=(h, w))["rgb"]
+    if 'crop' in views:
+        if crops is None:
+            raise ValueError("the crop panel needs the 224x224 crops")
+        cr = torch.as_tensor(crops, device=device).float()
+        out['crop'] = render_mesh(verts, cams, faces, cr.shape[1], color=color, bg_mode=L.RENDER_BG_FLOAT, bg_image=cr,
+                                  bg_add=1.0, bg_mul=127.5)["rgb"]
+    return out

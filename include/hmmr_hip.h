@@ -527,6 +527,59 @@ int hmmr_render_handoff(const float* cams, int64_t ld_cam, const float* verts, i
                         float* new_cam, float* proj_verts, float* kp_orig, void* stream);
 
 /* ------------------------------------------------------------------------- *
+ * Rasteriser for the demo views (csrc/render.hip): what src/util/render/nmr_renderer.py's VisRenderer asks of
+ * neural_renderer -- camera_mode='look_at', perspective=False, viewing angle 30 deg (eye at z = -2.7320508), near/far
+ * 0.1/100, fill_back, 2x anti-aliasing -- for n frames of one mesh topology per call.
+ *   projection   p = [s (x + tx), -s (y + ty), z] (VisRenderer.__call__), optionally after a rotation about the fp32
+ *                vertex centroid (VisRenderer.rotated) and after the camera change to the original image (geom rows,
+ *                as hmmr_render_handoff); depth z' = z + 2.7320508.
+ *   coverage     subpixel (c, r) of the 2S x 2S grid, centre u = (2c+1-2S)/2S, v = (2r+1-2S)/2S, is covered by a face
+ *                whose (p.x, -p.y) triangle contains (u, v) (edges included); depth 1 / sum(w_i / z'_i) in [0.1, 100];
+ *                the nearest wins, ties go to the lower face index.  Non-finite and zero-area faces draw nothing.
+ *   shading      tex (I_amb c_amb + I_dir c_dir max(0, n . d)), n = normalize(cross(p0-p1, p2-p1)) turned to n_z <= 0.
+ *   output       2x2 mean of the subpixels (background colour where uncovered), uint8 clip(rgb, 0, 1) 255 composited
+ *                over the background as trunc(img (1 - alpha) + rend alpha); alpha = covered subpixels / 4.
+ * The output is the top-left out_h x out_w of the S x S raster (make_square / remove_pads).
+ * ------------------------------------------------------------------------- */
+#define HMMR_RENDER_MAX_FRAMES 4096
+#define HMMR_RENDER_MIN_SIZE 16
+#define HMMR_RENDER_MAX_SIZE 1024
+#define HMMR_RENDER_MAX_FACES 65536
+enum { HMMR_RENDER_BG_COLOR = 0,      /* the background colour */
+       HMMR_RENDER_BG_FLOAT = 1,      /* float [n][S][S][3]: value = (img + bg_add) * bg_mul (fp32) */
+       HMMR_RENDER_BG_FRAME = 2 };    /* uint8 [n][frame_h][frame_w][3] frame, bilinearly resized to out_h x out_w as
+                                         cv2.resize does (visualize_img_orig): value = ((resized [-1,1] + 1) / 2) 255 */
+typedef struct {
+    const float* verts; int64_t ld_verts;     /* [n] rows of >= 3 nv floats (e.g. the verts field of packed records) */
+    const float* cams; int64_t ld_cam;        /* [n] rows of >= 3 floats: s, tx, ty */
+    const float* geom;                        /* NULL, or [n][5] {undo_scale, start_x, start_y, proc_size, img_size}:
+                                                 move the cameras to the original image first (hmmr_render_handoff) */
+    const int32_t* faces;                     /* [nf][3], indices in [0, nv): the caller's precondition */
+    const float* face_colors;                 /* NULL: `color` for every face; else rgb [nf][3] per frame row */
+    int64_t ld_face_colors;                   /* floats between frames' face_colors (0: one set for all frames) */
+    int n, nv, nf, size;                      /* frames, vertices, faces, S (the square raster is S x S pixels) */
+    int rotate;                               /* != 0: v <- rot (v - mean(v)) + mean(v) before projecting */
+    float rot[9];                             /* row-major 3x3 */
+    float color[3];                           /* mesh colour when face_colors == NULL */
+    float bg_color[3];
+    float light_dir[3];                       /* used as given (not normalised) */
+    float light_int_ambient, light_int_directional;
+    float light_color_ambient[3], light_color_directional[3];
+    int bg_mode;                              /* HMMR_RENDER_BG_* */
+    const void* bg_image;
+    float bg_add, bg_mul;                     /* HMMR_RENDER_BG_FLOAT */
+    int frame_h, frame_w;                     /* HMMR_RENDER_BG_FRAME */
+    int out_h, out_w;                         /* <= size */
+    unsigned char* rgb;                       /* [n][out_h][out_w][3] */
+    float* alpha;                             /* NULL or [n][out_h][out_w] */
+    int32_t* face_index;                      /* NULL or [n][2S][2S]: covering face, -1 where uncovered */
+    void* ws; size_t ws_bytes;                /* hmmr_render_workspace_bytes(n, nv, nf) bytes, device memory */
+} hmmr_render_desc_t;
+/* Device workspace for a call on n frames of an (nv, nf) mesh, at any size and background mode (0: bad arguments). */
+size_t hmmr_render_workspace_bytes(int n, int nv, int nf);
+int hmmr_render_mesh(const hmmr_render_desc_t* d, void* stream);
+
+/* ------------------------------------------------------------------------- *
  * Evaluation metrics on device (src/evaluation/eval_util.py): per-frame MPJPE after pelvis alignment
  * and after Procrustes alignment (compute_error_3d :30-60 with align_by_pelvis :158 and
  * compute_similarity_transform :177), acceleration (compute_accel :14) and acceleration error
