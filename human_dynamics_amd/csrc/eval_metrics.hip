@@ -5,8 +5,8 @@
 //   compute_accel        per interior frame: mean || X[i-1]-2X[i]+X[i+1] ||                     (:14-27)
 //   compute_error_verts  per frame: mean vertex distance                                        (:140-155)
 // so the joints / vertices that the SMPL stage leaves in HBM can be scored without a PCIe trip.
-// Inputs fp32, arithmetic fp64 (one lane per frame for the Procrustes problem: a 3x3 SVD by cyclic
-// Jacobi on K^T K; the work is a few hundred flops per frame, the kernel is latency-bound).
+// Inputs fp32, arithmetic fp64 (one lane per frame for the Procrustes problem: the right singular vectors of K by
+// cyclic Jacobi on K^T K, the left ones from K itself; a few hundred flops per frame, the kernel is latency-bound).
 #include "common.h"
 #include "hmmr_hip.h"
 
@@ -84,8 +84,11 @@ __global__ void eval_joints_kernel(const float* __restrict__ gt, const float* __
         for (int a = 0; a < 3; ++a)
             for (int b = 0; b < 3; ++b) K[a][b] += x1[a] * x2[b];              // K = X1 X2^T
     }
-    // K = U S V^T.  Eigen-decompose K^T K = V S^2 V^T, then U = K V S^-1 (third column by cross
-    // product when the smallest singular value vanishes).
+    // K = U S V^T.  Eigen-decompose K^T K = V S^2 V^T; the left vectors are the DIRECTIONS of K V, taken from K itself.
+    // (The singular values of the squared form carry an error of 1e-16 s0^2 / s: dividing K v by them, and deciding the
+    // rank by them, left a third column of noise whenever the smallest one vanishes without being an exact zero -- a
+    // planar gt or pred in general position.)  u0 = K v0 / |K v0|, u1 = the part of K v1 orthogonal to u0, u2 = u0 x u1:
+    // U is orthogonal whatever the rank, as LAPACK's is, and the sign in Z below makes R the proper rotation.
     double KtK[3][3], V[3][3];
     for (int a = 0; a < 3; ++a)
         for (int b = 0; b < 3; ++b) KtK[a][b] = K[0][a] * K[0][b] + K[1][a] * K[1][b] + K[2][a] * K[2][b];
@@ -94,20 +97,26 @@ __global__ void eval_joints_kernel(const float* __restrict__ gt, const float* __
     for (int a = 0; a < 2; ++a)
         for (int b = a + 1; b < 3; ++b)
             if (KtK[ord[b]][ord[b]] > KtK[ord[a]][ord[a]]) { const int t = ord[a]; ord[a] = ord[b]; ord[b] = t; }
-    double Vs[3][3], U[3][3], sv[3];
-    for (int i = 0; i < 3; ++i) {
-        sv[i] = sqrt(fmax(KtK[ord[i]][ord[i]], 0.0));
-        for (int r = 0; r < 3; ++r) Vs[r][i] = V[r][ord[i]];
-    }
+    double Vs[3][3], U[3][3];
     for (int i = 0; i < 3; ++i)
-        for (int r = 0; r < 3; ++r)
-            U[r][i] = sv[i] > 1e-12 * (sv[0] + 1e-300)
-                          ? (K[r][0] * Vs[0][i] + K[r][1] * Vs[1][i] + K[r][2] * Vs[2][i]) / sv[i] : 0.0;
-    if (!(sv[2] > 1e-12 * (sv[0] + 1e-300))) {                                   // rank-deficient: complete U
-        U[0][2] = U[1][0] * U[2][1] - U[2][0] * U[1][1];
-        U[1][2] = U[2][0] * U[0][1] - U[0][0] * U[2][1];
-        U[2][2] = U[0][0] * U[1][1] - U[1][0] * U[0][1];
+        for (int r = 0; r < 3; ++r) Vs[r][i] = V[r][ord[i]];
+    for (int i = 0; i < 2; ++i)
+        for (int r = 0; r < 3; ++r) U[r][i] = K[r][0] * Vs[0][i] + K[r][1] * Vs[1][i] + K[r][2] * Vs[2][i];
+    const double n0 = sqrt(U[0][0] * U[0][0] + U[1][0] * U[1][0] + U[2][0] * U[2][0]);   // = s0
+    for (int r = 0; r < 3; ++r) U[r][0] = n0 > 0.0 ? U[r][0] / n0 : (r == 0 ? 1.0 : 0.0);   // K == 0: any R (scale is 0 or 0 / 0)
+    const double d01 = U[0][0] * U[0][1] + U[1][0] * U[1][1] + U[2][0] * U[2][1];
+    for (int r = 0; r < 3; ++r) U[r][1] -= d01 * U[r][0];
+    double n1 = sqrt(U[0][1] * U[0][1] + U[1][1] * U[1][1] + U[2][1] * U[2][1]);
+    if (!(n1 > 1e-7 * n0)) {       // rank one at the precision of the squared form's vectors: any unit vector across u0
+        const int e = fabs(U[0][0]) <= fabs(U[1][0]) ? (fabs(U[0][0]) <= fabs(U[2][0]) ? 0 : 2)
+                                                     : (fabs(U[1][0]) <= fabs(U[2][0]) ? 1 : 2);
+        for (int r = 0; r < 3; ++r) U[r][1] = (r == e ? 1.0 : 0.0) - U[e][0] * U[r][0];
+        n1 = sqrt(U[0][1] * U[0][1] + U[1][1] * U[1][1] + U[2][1] * U[2][1]);
     }
+    for (int r = 0; r < 3; ++r) U[r][1] /= n1;
+    U[0][2] = U[1][0] * U[2][1] - U[2][0] * U[1][1];
+    U[1][2] = U[2][0] * U[0][1] - U[0][0] * U[2][1];
+    U[2][2] = U[0][0] * U[1][1] - U[1][0] * U[0][1];
     // R = V Z U^T with Z = diag(1, 1, sign(det(U V^T)))
     double UVt[3][3];
     for (int a = 0; a < 3; ++a)

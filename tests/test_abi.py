@@ -65,6 +65,64 @@ def test_argument_validation_reports_errors():
         _lib.check(rc, "hmmr_conv_gemm")
 
 
+def test_periphery_argument_validation_reports_errors():
+    """The entry points around the path (crop, hand-off, metrics) refuse what their kernels could not honour before
+    anything is launched -- dummy, never dereferenced pointers; no device is needed -- and leave a message."""
+    lib = _lib.load()
+    P = [0x1000 * (i + 1) for i in range(8)]
+
+    def refused(rc, *words):
+        msg = lib.hmmr_last_error()
+        assert rc != 0 and msg, (rc, msg)
+        for w in words:
+            assert w in msg, (w, msg)
+        with pytest.raises(_lib.HmmrError):
+            _lib.check(rc, "periphery")
+
+    def call(fn, names, defaults, kw):
+        args = dict(defaults)
+        args.update(kw)
+        return fn(*[args[a] for a in names.split()])
+
+    joints = lambda **kw: call(lib.hmmr_eval_joints, "gt pred n k l r mp pa ac ae st",
+                               dict(gt=P[0], pred=P[1], n=4, k=14, l=3, r=2, mp=P[2], pa=P[3], ac=None, ae=None, st=None), kw)
+    refused(joints(k=33), b"hmmr_eval_joints", b"k <= 32")                   # one past the per-lane array
+    refused(joints(k=0), b"hmmr_eval_joints")
+    refused(joints(n=0), b"hmmr_eval_joints")
+    for l, r in ((14, 2), (3, 14), (-1, 2), (3, -1)):
+        refused(joints(l=l, r=r), b"hmmr_eval_joints", b"hip ids")
+    refused(joints(k=2), b"hip ids")                                         # the LSP hips (3, 2) do not exist with 2 joints
+    refused(joints(pa=None), b"hmmr_eval_joints", b"both outputs")
+    refused(joints(mp=None), b"both outputs")
+    refused(joints(gt=None), b"needs gt")
+    refused(joints(pred=None), b"hmmr_eval_joints")
+
+    handoff = lambda **kw: call(lib.hmmr_render_handoff, "cams ldc verts ldv kps ldk geom n nv nk cam proj kp st",
+                                dict(cams=P[0], ldc=3, verts=P[1], ldv=3 * 50, kps=P[2], ldk=50, geom=None, n=2, nv=50, nk=25,
+                                     cam=P[3], proj=P[4], kp=P[5], st=None), kw)
+    refused(handoff(ldv=3 * 50 - 1), b"hmmr_render_handoff", b"row strides")
+    refused(handoff(ldc=2), b"row strides")
+    refused(handoff(ldk=49), b"row strides")
+    refused(handoff(kps=None), b"hmmr_render_handoff", b"kp_orig requested without kps")
+    refused(handoff(n=0), b"hmmr_render_handoff")
+    refused(handoff(nv=0), b"hmmr_render_handoff")
+    refused(handoff(nk=-1), b"hmmr_render_handoff")
+    refused(handoff(proj=None), b"hmmr_render_handoff")
+
+    crop = lambda **kw: call(lib.hmmr_crop_frames, "fr geom n h w out st",
+                             dict(fr=P[0], geom=P[1], n=1, h=96, w=128, out=P[2], st=None), kw)
+    refused(crop(n=0), b"hmmr_crop_frames")
+    refused(crop(h=0), b"hmmr_crop_frames")
+    refused(crop(geom=None), b"hmmr_crop_frames")
+    refused(crop(out=None), b"hmmr_crop_frames")
+
+    verts = lambda **kw: call(lib.hmmr_eval_verts, "gt ldg pred ldp n nv err st",
+                              dict(gt=P[0], ldg=150, pred=P[1], ldp=150, n=2, nv=50, err=P[2], st=None), kw)
+    refused(verts(nv=0), b"hmmr_eval_verts")
+    refused(verts(n=0), b"hmmr_eval_verts")
+    refused(verts(err=None), b"hmmr_eval_verts")
+
+
 def _dense_1x1(m=256, cin=64, cout=256, dtype=_lib.HMMR_F16X3):
     """a syntactically valid 1x1 descriptor with dummy (never dereferenced) pointers: validation runs before any launch"""
     d = _lib.ConvDesc()
