@@ -198,6 +198,11 @@ SIGNATURES = {
     "hmmr_render_mesh": (C.c_int, [C.POINTER(RenderDesc), _vp]),
     "hmmr_eval_joints": (C.c_int, [_fp, _fp, C.c_int, C.c_int, C.c_int, C.c_int, _fp, _fp, _fp, _fp, _vp]),
     "hmmr_eval_verts": (C.c_int, [_fp, C.c_int64, _fp, C.c_int64, C.c_int, C.c_int, _fp, _vp]),
+    "hmmr_eval_joints_ld": (C.c_int, [_fp, C.c_int64, _fp, C.c_int64, C.c_int, C.c_int, C.c_int, C.c_int, _fp, _fp, _fp, _fp, _vp]),
+    "hmmr_eval_kps": (C.c_int, [_fp, C.c_int64, _fp, C.c_int64, C.c_int, C.c_int, C.c_double, C.c_int, C.c_float,
+                                _fp, _fp, _fp, _fp, _vp]),
+    "hmmr_rotmat_to_axis_angle": (C.c_int, [_fp, C.c_int64, C.c_int, C.c_int, _fp, C.c_int64, _vp]),
+    "hmmr_axis_angle_to_rotmat": (C.c_int, [_fp, C.c_int64, C.c_int, C.c_int, _fp, C.c_int64, _vp]),
     "hmmr_global_rigid_transformation": (C.c_int, [_fp, _fp, _ip, C.c_int, _fp, _fp, C.c_int, _vp]),
     "hmmr_smpl_fwd_records": (C.c_int, [C.POINTER(SmplConsts), _fp, C.c_int, C.c_int, _fp, C.c_int64, C.POINTER(C.c_int32),
                                         _vp, C.c_size_t, _vp]),

@@ -22,6 +22,7 @@
 // 256 contiguous bytes per coordinate.
 #include "common.h"
 #include "hmmr_hip.h"
+#include "so3.h"
 
 static constexpr int NJ = 24;
 static constexpr int NFEAT = 218;        // 1 + 10 + 207
@@ -57,16 +58,7 @@ __global__ __launch_bounds__(256) void smpl_pose_kernel(
     float R[9] = {1, 0, 0, 0, 1, 0, 0, 0, 1};
     if (live) {
         const float* th = theta + (long long)inst * ld_theta + 3 * j;
-        const float x = th[0], y = th[1], z = th[2];
-        // batch_lbs.py:48-50: angle = ||theta + 1e-8||, r = theta / angle
-        const float ex = x + 1e-8f, ey = y + 1e-8f, ez = z + 1e-8f;
-        const float angle = sqrtf(ex * ex + ey * ey + ez * ez);
-        const float rx = x / angle, ry = y / angle, rz = z / angle;
-        const float c = cosf(angle), s = sinf(angle), oc = 1.0f - c;
-        // R = cos*I + (1-cos)*r r^T + sin*skew(r)      (batch_lbs.py:56-59, :24-36)
-        R[0] = c + oc * rx * rx;      R[1] = oc * rx * ry - s * rz; R[2] = oc * rx * rz + s * ry;
-        R[3] = oc * ry * rx + s * rz; R[4] = c + oc * ry * ry;      R[5] = oc * ry * rz - s * rx;
-        R[6] = oc * rz * rx - s * ry; R[7] = oc * rz * ry + s * rx; R[8] = c + oc * rz * rz;
+        rodrigues_f32(th[0], th[1], th[2], R);      // so3.h
         if (rs) {
             float* o = rec_ptr(rs, inst, ld_rs, rm, F_POSES) + j * 9;
 #pragma unroll

@@ -592,6 +592,30 @@ int hmmr_eval_joints(const float* gt, const float* pred, int n, int k, int left_
  * packed per-frame record). */
 int hmmr_eval_verts(const float* gt, int64_t ld_gt, const float* pred, int64_t ld_pred, int n, int nv,
                     float* err, void* stream);
+/* hmmr_eval_joints with row strides in floats (>= 3 k): the first k joints of a wider row -- preds['joints'][:, :14] inside the
+ * packed per-frame record -- are read in place.  Same device code; with ld = 3 k the same bits as hmmr_eval_joints. */
+int hmmr_eval_joints_ld(const float* gt, int64_t ld_gt, const float* pred, int64_t ld_pred, int n, int k,
+                        int left_id, int right_id, float* mpjpe, float* pa_mpjpe, float* accel_pred, float* accel_err,
+                        void* stream);
+/* compute_error_kp with compute_opt_cam_with_vis (eval_util.py:97-137, :235-260), one frame per lane, k <= 32.
+ * kps_gt [n][k][3] = (x, y, vis) with row stride ld_gt >= 3 k, kps_pred [n][k][2] with row stride ld_pred >= 2 k (floats).
+ * img_size > 0: the prediction is mapped to image space first, (x + 1) * 0.5 * img_size as three fp32 operations
+ * (compute_errors_batched, eval.py:131, in float32); img_size <= 0: it is in pixels already.  vis = (gt[:, 2] != 0).
+ * Outputs, each optional: err_kp / err_kp_pa / pck [n] and cam [n][3] = [scale, tx, ty].  Means over the visible keypoints;
+ * the alignment keeps the reference's 1e-6 I regulariser and trace(.) / 2; pck = share of visible keypoints whose aligned
+ * distance is strictly below alpha.  A frame without a visible keypoint, or with fewer than min_visible, gets NaN in every
+ * output: a result, not an error (hmmr_run_flags is not touched). */
+int hmmr_eval_kps(const float* kps_gt, int64_t ld_gt, const float* kps_pred, int64_t ld_pred, int n, int k,
+                  double alpha, int min_visible, float img_size, float* err_kp, float* err_kp_pa, float* pck,
+                  float* cam, void* stream);
+/* rot_mat_to_axis_angle / axis_angle_to_rot_mat (eval_util.py:318-343) without OpenCV.  n rows of `per` rotations each:
+ * rot rows hold `per` row-major 3x3 matrices (stride ld_rot >= 9 per floats; preds['poses'] inside the packed record), aa rows
+ * `per` vectors (stride ld_aa >= 3 per).  The log map returns w with |w| <= pi and Rodrigues(w) = R, conditioned over the whole
+ * range (atan2 of the antisymmetric norm and the trace; beyond a quarter turn the axis comes from the symmetric part, so nothing
+ * is divided by sin near pi; at exactly pi either sign is right).  fp64 arithmetic on the fp32 input.  The exp map is the fp32
+ * Rodrigues of the SMPL pose kernel (batch_rodrigues, src/tf_smpl/batch_lbs.py:42-60). */
+int hmmr_rotmat_to_axis_angle(const float* rot, int64_t ld_rot, int n, int per, float* aa, int64_t ld_aa, void* stream);
+int hmmr_axis_angle_to_rotmat(const float* aa, int64_t ld_aa, int n, int per, float* rot, int64_t ld_rot, void* stream);
 
 /* ------------------------------------------------------------------------- *
  * Packers (ABI 18; csrc/pack.cpp): checkpoint variables by name -> the layouts and structs above, WITHOUT Python.
