@@ -135,6 +135,9 @@ class SmplSource(C.Structure):
 
 RENDER_MAX_FRAMES, RENDER_MIN_SIZE, RENDER_MAX_SIZE, RENDER_MAX_FACES = 4096, 16, 1024, 65536
 RENDER_BG_COLOR, RENDER_BG_FLOAT, RENDER_BG_FRAME = 0, 1, 2
+# hmmr_track_* (csrc/track.hip): limits, the gap scan's step, the status bits of hmmr_track_crop_geom
+TRACK_MAX_KPS, TRACK_MAX_KERNEL, TRACK_MAX_RADIUS, TRACK_MAX_ROWS, TRACK_TILE = 64, 31, 64, 1 << 27, 256
+TRACK_EMPTY, TRACK_BEFORE_ORIGIN, TRACK_CLIPPED, TRACK_NOT_FINITE = 1, 2, 4, 8
 
 
 class RenderDesc(C.Structure):
@@ -185,6 +188,11 @@ SIGNATURES = {
     "hmmr_smpl_fwd": (C.c_int, [C.POINTER(SmplConsts), _fp, C.c_int, _fp, C.c_int, _fp, C.c_int, C.c_int,
                                 _fp, _fp, _fp, _fp, _vp, C.c_size_t, _vp]),
     "hmmr_crop_frames": (C.c_int, [_vp, _ip, C.c_int, C.c_int, C.c_int, _fp, _vp]),
+    "hmmr_track_workspace_bytes": (C.c_size_t, [C.c_int, C.c_int]),
+    "hmmr_track_bbox": (C.c_int, [_fp, _vp, C.POINTER(C.c_int32), C.c_int, C.c_int, C.c_double, C.c_int, C.POINTER(C.c_double), C.c_int,
+                                  _fp, _fp, _ip, _vp, C.c_size_t, _vp]),
+    "hmmr_track_smooth": (C.c_int, [_fp, C.POINTER(C.c_int32), C.c_int, C.c_int, C.POINTER(C.c_double), C.c_int, _fp, _vp, C.c_size_t, _vp]),
+    "hmmr_track_crop_geom": (C.c_int, [_fp, C.POINTER(C.c_int32), _ip, C.c_int, C.c_int, C.c_int, _ip, _fp, _ip, _vp]),
     "hmmr_bottleneck_tail": (C.c_int, [C.POINTER(TailDesc), _vp]),
     "hmmr_pair_stream_bytes": (C.c_size_t, [C.c_int, C.c_int, C.c_int]),
     "hmmr_b1_unit_stream_bytes": (C.c_size_t, [C.c_int]),

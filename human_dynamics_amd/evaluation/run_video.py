@@ -5,6 +5,11 @@
 returns the [n,224,224,3] float32 crops in [-1,1] as a DEVICE tensor (ready for
 Tester.predict_all_images / ShardedPredictor) plus, per frame, the dict fields of the reference
 (`im_shape`, `center`, `scale`, `start_pt`).  Decoding (imread) stays with the caller.
+
+    per_track = process_tracks(frames_uint8[F,H,W,3], tracks_kps, vis_thresh=0.1)
+
+is the front of demo_video.predict_on_tracks (:136-153) for any number of person tracks of one video: keypoints -> smoothed
+boxes (util/smooth_bbox.py) -> crop integers -> crops, all on the device, with one download (ranges, status, info) at the end.
 """
 from __future__ import annotations
 
@@ -12,6 +17,8 @@ import numpy as np
 import torch
 
 from .. import _lib as L
+from ..util import smooth_bbox
+from .tracks import pack_tracks
 
 IMG_SIZE = 224
 
@@ -49,3 +56,68 @@ def process_images(frames, bbox_params, device="cuda:0"):
     L.check(lib.hmmr_crop_frames(fr.data_ptr(), geom.data_ptr(), n, h, w, out.data_ptr(),
                                  torch.cuda.current_stream(device).cuda_stream), "hmmr_crop_frames")
     return out, [{k: g[k] for k in ("im_shape", "center", "scale", "start_pt")} for g in infos]
+
+
+def process_tracks(frames, tracks_kps, vis_thresh=0.1, kernel_size=11, sigma=3, device="cuda:0"):
+    """frames: [F,H,W,3] uint8 (RGB), a device tensor or a host array that is uploaded once.  tracks_kps: [track][frame] ->
+    (K,3) keypoints or None, frame i of every track being frames[i] (evaluation/tracks.get_labels_poseflow).
+
+    Returns, per track, (crops, (start, end), infos): the [end-start,224,224,3] float32 device crops of frames[start:end] with
+    the track's smoothed boxes -- bit for bit process_images(frames[start:end], smoothed[start:end]) -- and the images_orig
+    dicts of those frames.  Nothing comes to the host between the keypoint upload and the one download at the end; a box that
+    gives no full crop (or a track without a box) raises ValueError there, naming the track and its first bad frame.
+
+    The extent of a track is not known on the host before that download, so every row of a track is cropped (rows outside
+    [start, end) with the identity geometry) and `crops` is a view of rows [start, end) of a [len(track),224,224,3] buffer: a
+    track with long leading or trailing gaps pays the crop work and keeps about 602 KB per unused frame alive for as long as
+    the view lives.  `crops.clone()` releases it."""
+    lib = L.load()
+    if isinstance(frames, torch.Tensor):
+        fr = frames.to(device).contiguous()
+    else:
+        fr = torch.from_numpy(np.ascontiguousarray(frames)).to(device)
+    assert fr.dtype == torch.uint8 and fr.dim() == 4 and fr.shape[3] == 3, "frames: [F,H,W,3] uint8 (RGB)"
+    n_frames, h, w = fr.shape[:3]
+    tracks_kps = [list(trk) for trk in tracks_kps]
+    if not tracks_kps:
+        return []
+    for t, trk in enumerate(tracks_kps):
+        if not 1 <= len(trk) <= n_frames:
+            raise ValueError("track %d has %d entries for %d frames" % (t, len(trk), n_frames))
+    kps, present, offsets = pack_tracks(tracks_kps)
+    n, n_tracks = int(offsets[-1]), len(tracks_kps)
+    dev, stream = fr.device, torch.cuda.current_stream(fr.device).cuda_stream
+    smooth, rng, _ = smooth_bbox.track_boxes(torch.from_numpy(kps).to(dev), torch.from_numpy(present).to(dev), offsets, vis_thresh,
+                                             kernel_size, sigma)
+    # what the host needs at the end, in one buffer: info [N][5] float64 | range [T][2] int32 | status [N] int32
+    blob = torch.empty(n * 40 + n_tracks * 8 + n * 4, dtype=torch.uint8, device=dev)
+    info, rng_out, status = blob[:n * 40].view(torch.float64), blob[n * 40:n * 40 + n_tracks * 8].view(torch.int32), blob[n * 40 + n_tracks * 8:].view(torch.int32)
+    geom = torch.empty((n, 4), dtype=torch.int32, device=dev)
+    off_p = offsets.ctypes.data_as(L.C.POINTER(L.C.c_int32))
+    L.check(lib.hmmr_track_crop_geom(smooth.data_ptr(), off_p, rng.data_ptr(), n_tracks, h, w, geom.data_ptr(), info.data_ptr(),
+                                     status.data_ptr(), stream), "hmmr_track_crop_geom")
+    rng_out.copy_(rng.reshape(-1))
+    # every row of a track is cropped (rows outside [start, end) with the identity geometry): the extent is not known here
+    crops = []
+    for t in range(n_tracks):
+        o, nt = int(offsets[t]), int(offsets[t + 1] - offsets[t])
+        out = torch.empty((nt, IMG_SIZE, IMG_SIZE, 3), dtype=torch.float32, device=dev)
+        L.check(lib.hmmr_crop_frames(fr.data_ptr(), geom[o:].data_ptr(), nt, h, w, out.data_ptr(), stream), "hmmr_crop_frames")
+        crops.append(out)
+    host = blob.cpu().numpy()                                                   # the one synchronisation point
+    info_h = host[:n * 40].view(np.float64).reshape(n, 5)
+    rng_h = host[n * 40:n * 40 + n_tracks * 8].view(np.int32).reshape(n_tracks, 2)
+    status_h = host[n * 40 + n_tracks * 8:].view(np.int32)
+    results = []
+    for t in range(n_tracks):
+        o, (start, end) = int(offsets[t]), (int(rng_h[t, 0]), int(rng_h[t, 1]))
+        if start < 0:
+            raise ValueError("track %d: no frame has a bounding box" % t)
+        bad = np.flatnonzero(status_h[o:o + end])
+        if len(bad):
+            raise ValueError("track %d: the smoothed box of frame %d does not yield a full 224x224 crop of a %dx%d frame (status %d; "
+                             "%d such frames)" % (t, bad[0], h, w, status_h[o + bad[0]], len(bad)))
+        infos = [{"im_shape": [IMG_SIZE, IMG_SIZE], "center": row[2:4].astype(int), "scale": float(row[4]), "start_pt": row[:2].astype(int)}
+                 for row in info_h[o + start:o + end]]
+        results.append((crops[t][start:end], (start, end), infos))
+    return results

@@ -512,6 +512,60 @@ int hmmr_crop_frames(const unsigned char* frames, const int32_t* geom, int n, in
                      float* out, void* stream);
 
 /* ------------------------------------------------------------------------- *
+ * Track front end (csrc/track.hip): from a person track's 2D keypoints to the geom rows hmmr_crop_frames reads, without a
+ * host step.  Replaces src/util/smooth_bbox.py (get_smooth_bbox_params :10-34, kp_to_bbox_param :37-61, get_all_bbox_params
+ * :64-105, smooth_bbox_params :108-123) and the per-frame arithmetic of demo_video.predict_on_tracks :136-153 with
+ * process_image (src/evaluation/run_video.py:56-107) and resize_img (src/util/common.py:7-14).  fp64 throughout.
+ *
+ * Tracks lie one after the other along the row axis: track t owns rows [offsets[t], offsets[t + 1]).  `offsets` is HOST memory
+ * (n_tracks + 1 values, non-decreasing, offsets[0] >= 0, at most HMMR_TRACK_MAX_ROWS rows); it is checked and then handed to
+ * the kernels by value.  gauss_w is HOST memory too: the 2 radius + 1 weights of scipy.ndimage.gaussian_filter1d
+ * (exp(-x^2 / 2 sigma^2) normalised to sum 1, radius = int(4 sigma + 0.5)), computed once by the caller; the filter is taken as
+ * symmetric, so gauss_w[0 .. radius] is what is read.  Everything else is device memory.  Nothing is allocated, nothing waits for
+ * the device, no atomics: the same bits every run.  Bad arguments are refused before any launch (-1, hmmr_last_error()).
+ *
+ * hmmr_track_bbox
+ *   kps [N][k][3] = (x, y, score), 1 <= k <= HMMR_TRACK_MAX_KPS; present [N]: 0 = the reference's None.
+ *   A row is valid if it is present, a score is strictly greater than vis_thresh and person_height = |max_pt - min_pt| over
+ *   the visible keypoints is >= 0.5; then box = [(min_pt + max_pt) / 2, 150 / person_height].
+ *   range [n_tracks][2] = {start, end} relative to the track's first row: the first valid row and one past the last one
+ *   (-1, 0: no valid row).  Invalid rows between valid rows p < i < q get prev + (i - p) * ((curr - prev) / (q - p)), which is
+ *   np.linspace's arithmetic; gaps of any length (the scan works in steps of HMMR_TRACK_TILE rows with a carry).
+ *   bbox_raw [N][3] (may be NULL): the rows of get_all_bbox_params at start..end-1, zero elsewhere.
+ *   bbox_smooth [N][3]: over rows [start, end) and per parameter scipy.signal.medfilt(x, kernel_size) -- the window is padded
+ *   with ZEROS, kernel_size odd in [1, HMMR_TRACK_MAX_KERNEL] -- then the Gaussian with boundary mode 'reflect'
+ *   (d c b a | a b c d | d c b a, repeated as often as the radius asks; radius <= HMMR_TRACK_MAX_RADIUS), summed in SciPy's
+ *   order.  Neither filter reads a neighbouring track.  Rows outside [start, end) are zero.
+ *   ws: hmmr_track_workspace_bytes(offsets[n_tracks], n_tracks) bytes (0: bad arguments).
+ * hmmr_track_smooth: smooth_bbox_params alone, over all rows of every track of params [N][3] -> out [N][3].
+ * hmmr_track_crop_geom
+ *   for every row of [start, end) (range == NULL: every row) the integers of process_image for box bbox_smooth[row] on an
+ *   h x w frame: geom [N][4] = {floor(h scale), floor(w scale), u0, v0} as hmmr_crop_frames reads them, with
+ *   centre = round(c * factors) + 224 (x by the HEIGHT factor, y by the WIDTH factor, as the reference has it),
+ *   start_pt = centre - 112, u0 / v0 = start_pt - 224; info [N][5] (may be NULL) = {start_pt x, y, centre - start_pt x, y,
+ *   scale}.  A row whose box gives no full 224 x 224 crop gets a status [N] of HMMR_TRACK_* bits and the identity geometry
+ *   {h, w, 0, 0}, which hmmr_crop_frames can execute; so do rows outside [start, end), with status 0.  A bad box is
+ *   reported, never a fault, and hmmr_run_flags is not touched.
+ * ------------------------------------------------------------------------- */
+#define HMMR_TRACK_MAX_KPS 64
+#define HMMR_TRACK_MAX_KERNEL 31
+#define HMMR_TRACK_MAX_RADIUS 64
+#define HMMR_TRACK_MAX_ROWS (1 << 27)
+#define HMMR_TRACK_TILE 256           /* rows per step of the gap scan: no limit, only where tests look for seams */
+enum { HMMR_TRACK_EMPTY = 1,          /* floor(h scale) or floor(w scale) < 1 */
+       HMMR_TRACK_BEFORE_ORIGIN = 2,  /* start_pt < 0 */
+       HMMR_TRACK_CLIPPED = 4,        /* the crop's end point lies beyond the padded image */
+       HMMR_TRACK_NOT_FINITE = 8 };   /* NaN, infinity or a value no int32 holds */
+size_t hmmr_track_workspace_bytes(int n_total, int n_tracks);
+int hmmr_track_bbox(const double* kps, const unsigned char* present, const int32_t* offsets, int n_tracks, int k,
+                    double vis_thresh, int kernel_size, const double* gauss_w, int gauss_radius, double* bbox_raw,
+                    double* bbox_smooth, int32_t* range, void* ws, size_t ws_bytes, void* stream);
+int hmmr_track_smooth(const double* params, const int32_t* offsets, int n_tracks, int kernel_size, const double* gauss_w,
+                      int gauss_radius, double* out, void* ws, size_t ws_bytes, void* stream);
+int hmmr_track_crop_geom(const double* bbox_smooth, const int32_t* offsets, const int32_t* range, int n_tracks, int h, int w,
+                         int32_t* geom, double* info, int32_t* status, void* stream);
+
+/* ------------------------------------------------------------------------- *
  * Hand-off to a rasteriser after the path (SURVEY f-3).  Replaces, for n frames in one launch, the
  * per-frame host code of src/util/render/nmr_renderer.py: the camera / keypoint change from the
  * 224x224 crop to the squared original image (visualize_img_orig :368-401) and the projection that
