@@ -153,6 +153,22 @@ class RenderDesc(C.Structure):
                 ("rgb", _vp), ("alpha", _fp), ("face_index", _ip), ("ws", _vp), ("ws_bytes", C.c_size_t)]
 
 
+SKELETON_MAX_RADIUS, COLLAGE_MAX_PANEL_WIDTH = 1024, 4096
+
+
+class SkeletonDesc(C.Structure):
+    """hmmr_skeleton_desc_t: one call of the skeleton panel (csrc/collage.hip)"""
+    _fields_ = [("kps", _fp), ("ld_kps", C.c_int64), ("vis", _vp), ("n", C.c_int), ("nk", C.c_int), ("h", C.c_int), ("w", C.c_int),
+                ("kp_add", C.c_float), ("kp_mul", C.c_float), ("draw_edges", C.c_int), ("radius", C.c_int),
+                ("bg_float", _fp), ("bg_add", C.c_float), ("bg_mul", C.c_float), ("bg_u8", _vp), ("out", _vp)]
+
+
+class CollageDesc(C.Structure):
+    """hmmr_collage_desc_t: one call of the 2x2 collage (csrc/collage.hip)"""
+    _fields_ = [("rend_crop", _vp), ("skel_crop", _vp), ("render_og", _vp), ("rot_og", _vp),
+                ("n", C.c_int), ("S", C.c_int), ("h", C.c_int), ("w", C.c_int), ("out", _vp)]
+
+
 # name -> (restype, argtypes); mirrors include/hmmr_hip.h one to one
 SIGNATURES = {
     "hmmr_abi_version": (C.c_int, []),
@@ -204,6 +220,10 @@ SIGNATURES = {
                                       _fp, _fp, _fp, _vp]),
     "hmmr_render_workspace_bytes": (C.c_size_t, [C.c_int, C.c_int, C.c_int]),
     "hmmr_render_mesh": (C.c_int, [C.POINTER(RenderDesc), _vp]),
+    "hmmr_skeleton_radius": (C.c_int, [C.c_int, C.c_int]),
+    "hmmr_draw_skeleton": (C.c_int, [C.POINTER(SkeletonDesc), _vp]),
+    "hmmr_collage_width": (C.c_int, [C.c_int, C.c_int, C.c_int]),
+    "hmmr_compose_collage": (C.c_int, [C.POINTER(CollageDesc), _vp]),
     "hmmr_eval_joints": (C.c_int, [_fp, _fp, C.c_int, C.c_int, C.c_int, C.c_int, _fp, _fp, _fp, _fp, _vp]),
     "hmmr_eval_verts": (C.c_int, [_fp, C.c_int64, _fp, C.c_int64, C.c_int, C.c_int, _fp, _vp]),
     "hmmr_eval_joints_ld": (C.c_int, [_fp, C.c_int64, _fp, C.c_int64, C.c_int, C.c_int, C.c_int, C.c_int, _fp, _fp, _fp, _fp, _vp]),

@@ -10,8 +10,20 @@ Tester.predict_all_images / ShardedPredictor) plus, per frame, the dict fields o
 
 is the front of demo_video.predict_on_tracks (:136-153) for any number of person tracks of one video: keypoints -> smoothed
 boxes (util/smooth_bbox.py) -> crop integers -> crops, all on the device, with one download (ranges, status, info) at the end.
+
+    render_preds(output_path, config, preds, images, images_orig, trim_length)
+
+is `render_preds` (:110-202): the 2x2 collage frames and the full-size mesh-on-original frames of one track, rendered in
+chunks on the device (util/render/video.render_views), written as PNGs with PIL and, where an ffmpeg is installed, turned
+into the two mp4s by the reference's command line.  The skeleton's draw list is the reference's; the pixels of its
+primitives follow the integer rules of include/hmmr_hip.h, whose agreement with OpenCV at primitive boundaries has not been
+measured; no text is drawn.
 """
 from __future__ import annotations
+
+import os
+import shutil
+import subprocess
 
 import numpy as np
 import torch
@@ -121,3 +133,87 @@ def process_tracks(frames, tracks_kps, vis_thresh=0.1, kernel_size=11, sigma=3, 
                  for row in info_h[o + start:o + end]]
         results.append((crops[t][start:end], (start, end), infos))
     return results
+
+
+def _ffmpeg_command(output_path, img_dir, fps=25):
+    """make_video's command line (:205-225)"""
+    return ['ffmpeg', '-y', '-threads', '16', '-framerate', str(fps), '-i', '{}/frame%06d.png'.format(img_dir),
+            '-profile:v', 'baseline', '-level', '3.0', '-c:v', 'libx264', '-pix_fmt', 'yuv420p', '-an',
+            '-vf', 'scale=trunc(iw/2)*2:trunc(ih/2)*2', output_path]
+
+
+def make_video(output_path, img_dir, fps=25):
+    """Runs ffmpeg over img_dir/frame%06d.png if there is one: True (written), False (ffmpeg failed) or None (no ffmpeg)."""
+    if shutil.which('ffmpeg') is None:
+        return None
+    cmd = _ffmpeg_command(output_path, img_dir, fps)
+    print(' '.join(cmd))
+    try:
+        return subprocess.call(cmd) == 0
+    except OSError:
+        return False
+
+
+def _read_frames(images_orig, lo, hi):
+    from PIL import Image
+    return np.stack([np.asarray(Image.open(images_orig[j]['im_path']).convert("RGB")) for j in range(lo, hi)])
+
+
+def render_preds(output_path, config, preds, images, images_orig, trim_length, img_size=224, frames=None, faces=None,
+                 face_path='src/tf_smpl/smpl_faces.npy', chunk=64, device=None):
+    """Renders frames [trim_length, len - trim_length) of one track as the reference does:
+
+        output_path/frame%06d.png            the mesh over the original frame (down-scaled to at most 720 pixels)
+        output_path + '_crop'/frame%06d.png  | mesh on the crop   | mesh on the original frame |
+                                             | skeleton on crop   | mesh rotated 90 degrees    |
+
+    preds: predict_all_images' dict (cams, kps, verts; host arrays or device tensors); images: the img_size crops in [-1, 1];
+    images_orig: process_image's dicts (im_path, start_pt, scale, im_shape).  frames: the original frames uint8 [n,H,W,3]
+    (host or device) instead of reading im_path with PIL; faces: [F,3] instead of reading face_path.
+    Returns None if output_path + '.mp4' exists already ("Video already exists!"), else a dict: the two folders, the number
+    of frames written, and `videos`: the mp4 paths, or None with `note` saying that no ffmpeg was found and the PNG frames
+    were left in place."""
+    from PIL import Image
+    from ..util.render import video
+    from ..util.render.nmr_renderer import load_faces
+    from ..util.render.raster import MeshFaces
+    max_img_size = 720
+    output_crop = output_path + '_crop'
+    vid_path, vid_path_crop = output_path + '.mp4', output_crop + '.mp4'
+    if os.path.exists(vid_path):
+        print('Video already exists!')
+        return None
+    for d in (output_path, output_crop):
+        if not os.path.exists(d):
+            os.mkdir(d)
+    if device is None:
+        v = preds['verts']
+        device = v.device if torch.is_tensor(v) and v.device.type == "cuda" else torch.device("cuda", torch.cuda.current_device())
+    mesh_faces = faces if isinstance(faces, MeshFaces) else MeshFaces(faces if faces is not None else load_faces(face_path))
+    lo, hi = trim_length, len(preds['kps']) - trim_length
+    written = 0
+    for a in range(lo, hi, chunk):
+        b = min(a + chunk, hi)
+        part = {k: preds[k][a:b] for k in ('cams', 'kps', 'verts')}
+        fr = frames[a:b] if frames is not None else _read_frames(images_orig, a, b)
+        crops = images[a:b] if torch.is_tensor(images) else np.stack([np.asarray(images[j], np.float32) for j in range(a, b)])
+        if tuple(crops.shape[1:3]) != (img_size, img_size):
+            raise ValueError("crops of %s for img_size = %d" % (tuple(crops.shape[1:3]), img_size))
+        out = video.render_views(part, None, fr, images_orig[a:b], mesh_faces, crops=crops, views=('collage',),
+                                 max_img_size=max_img_size, mesh_color=config.mesh_color, device=device)
+        full, collage = out['orig'].cpu().numpy(), out['collage'].cpu().numpy()
+        for j in range(a, b):
+            name = 'frame{:06d}.png'.format(j - trim_length)
+            Image.fromarray(full[j - a]).save(os.path.join(output_path, name))
+            Image.fromarray(collage[j - a]).save(os.path.join(output_crop, name))
+            written += 1
+    print('Converting them to video..')
+    made = [make_video(vid_path, output_path), make_video(vid_path_crop, output_crop)]
+    result = {"frames": output_path, "frames_crop": output_crop, "n_frames": written, "videos": None, "note": None}
+    if made[0] is None:
+        result["note"] = "no ffmpeg on PATH: the PNG frames are left in %s and %s" % (output_path, output_crop)
+    elif all(made):
+        result["videos"] = (vid_path, vid_path_crop)
+    else:
+        result["note"] = "ffmpeg failed: the PNG frames are left in %s and %s" % (output_path, output_crop)
+    return result

@@ -2,8 +2,11 @@
 project's own rasteriser (csrc/render.hip) instead of neural_renderer, which does not exist for ROCm.
 
 The reference's `visualize_img`, `visualize_img_orig` and `render_preds` run unchanged on top of it for their mesh
-panels (they set `.renderer.image_size` and call `__call__` / `rotated`); their skeleton and text drawing, the collage
-and the PNG / video writing need cv2 and stay with the caller.  Inputs may be numpy arrays or device tensors; results
+panels (they set `.renderer.image_size` and call `__call__` / `rotated`).  The module-level `visualize_img` and
+`visualize_img_orig` below are the reference's functions of those names (:265-419) without cv2: the skeleton comes from
+util/render/collage.draw_skeleton, whose draw list is the reference's and whose primitives follow the integer rules of
+include/hmmr_hip.h -- agreement with OpenCV's circles and lines at primitive boundaries has not been measured -- and
+`draw_text` (cv2.putText) is not provided: they take `no_text=True` only.  Inputs may be numpy arrays or device tensors; results
 are what the reference returns (uint8 numpy: [S,S,3], [B,S,S,3], RGBA [S,S,4], or the silhouette), or the same data as
 device tensors with `on_device=True`.  Only t_size = 1 textures (one colour per face) are supported.
 """
@@ -14,6 +17,7 @@ import torch
 
 from ... import _lib as L
 from ...tf_smpl.batch_smpl import _SmplUnpickler
+from .collage import draw_skeleton
 from .raster import COLORS, MeshFaces, render_mesh, rodrigues
 
 colors = COLORS
@@ -149,4 +153,109 @@ class VisRenderer(object):
         self.renderer.background_color = color
 
 
-__all__ = ["VisRenderer", "colors", "load_faces"]
+def _host(x):
+    return x.cpu().numpy() if isinstance(x, torch.Tensor) else x
+
+
+def make_square(img):
+    """Pads the shorter side with zeros at its end (the rasteriser draws squares): (img, pad_vals)."""
+    img_size = np.max(img.shape[:2])
+    pad_vals = img_size - np.array(img.shape[:2])
+    return np.pad(img, ((0, pad_vals[0]), (0, pad_vals[1]), (0, 0)), mode='constant'), pad_vals
+
+
+def remove_pads(img, pad_vals):
+    """Undoes make_square."""
+    if pad_vals[0] != 0:
+        img = img[:-pad_vals[0], :]
+    if pad_vals[1] != 0:
+        img = img[:, :-pad_vals[1]]
+    return img
+
+
+def _resize_linear(img, h, w):
+    """cv2.resize(img, (w, h)) of a float image as csrc/image_geom.h's taps have it: pixel centres aligned in float32,
+    float32 weights, float64 sums, the horizontal pass first (resize_img of src/util/common.py)."""
+    def taps(src, dst):
+        f = ((np.arange(dst) + 0.5) * (float(src) / float(dst)) - 0.5).astype(np.float32)
+        s = np.floor(f).astype(np.int64)
+        f = f - s.astype(np.float32)
+        edge = (s < 0) | (s >= src - 1)
+        s = np.clip(s, 0, src - 1)
+        f[edge] = 0
+        return s, np.minimum(s + 1, src - 1), (np.float32(1) - f).astype(np.float64), f.astype(np.float64)
+    x0, x1, a0, a1 = taps(img.shape[1], w)
+    y0, y1, b0, b1 = taps(img.shape[0], h)
+    img = np.asarray(img, np.float64)
+    rows = img[:, x0] * a0[None, :, None] + img[:, x1] * a1[None, :, None]
+    return rows[y0] * b0[:, None, None] + rows[y1] * b1[:, None, None]
+
+
+def _no_text(text, no_text):
+    if not no_text or text:
+        raise NotImplementedError("draw_text (cv2.putText, a Hershey font) is not provided: call with no_text=True and no text")
+
+
+def visualize_img(img, cam, kp_pred, vert, renderer, kp_gt=None, text={}, rotated_view=False, mesh_color='blue',
+                  pad_vals=None, no_text=False):
+    """img [S,S,3] in [-1, 1], keypoints in normalised coordinates -> (skel_img / 255, rend_img / 255[, rot_img / 255]):
+    the predicted skeleton (and kp_gt's visible joints as rings) over the image, the mesh over the image, the mesh turned
+    by 90 degrees.  pad_vals: what make_square added, removed again from every panel."""
+    _no_text(text, no_text)
+    img = _host(img)
+    img_size = img.shape[0]
+    input_img = ((img + 1) * 0.5) * 255.
+    rend_img = _host(renderer(vert, cam=cam, img=input_img, color_name=mesh_color))
+    kp_pred = _host(kp_pred)
+    skel_img = draw_skeleton(input_img, ((kp_pred + 1) * 0.5) * img_size)
+    if kp_gt is not None:
+        kp_gt = _host(kp_gt)
+        skel_img = draw_skeleton(skel_img, ((kp_gt[:, :2] + 1) * 0.5) * img_size, draw_edges=False,
+                                 vis=kp_gt[:, 2].astype(bool))
+    panels = [skel_img, rend_img]
+    if rotated_view:
+        panels.append(_host(renderer.rotated(vert, 90, cam=cam, alpha=False, color_name=mesh_color)))
+    if pad_vals is not None:
+        panels = [remove_pads(p, pad_vals) for p in panels]
+    return tuple(p / 255 for p in panels)
+
+
+def visualize_img_orig(cam, kp_pred, vert, renderer, start_pt, scale, proc_img_shape, im_path=None, img=None,
+                       rotated_view=False, mesh_color='blue', max_img_size=300, no_text=False, bbox=None, crop_cam=None):
+    """visualize_img in the space of the original image: img in [-1, 1] (or im_path, read with PIL), down-scaled to
+    max_img_size, squared, with the camera and the keypoints moved from the crop (start_pt, scale, proc_img_shape are
+    process_image's) to it."""
+    _no_text(None, no_text)
+    if img is None:
+        from PIL import Image
+        img = ((np.asarray(Image.open(im_path).convert("RGB")) / 255.) - 0.5) * 2
+    img = _host(img)
+    undo_scale = 1. / np.array(scale)
+    if np.max(img.shape[:2]) > max_img_size:
+        scale_orig = max_img_size / float(np.max(img.shape[:2]))
+        new_hw = np.floor(np.array(img.shape[:2]) * scale_orig).astype(int)
+        img = _resize_linear(img, new_hw[0], new_hw[1])
+        undo_scale = undo_scale * scale_orig
+    if bbox is not None:
+        assert crop_cam is not None
+        img = img[bbox[0]:bbox[1], bbox[2]:bbox[3]]
+        start_pt = np.array([0, 0])
+    img, pad_vals = make_square(img)
+    img_size = np.max(img.shape[:2])
+    renderer.renderer.image_size = img_size
+    proc = proc_img_shape[0]
+    pred_joint_orig = (((_host(kp_pred) + 1) * 0.5) * proc + start_pt - proc) * undo_scale
+    kp_orig = 2 * (pred_joint_orig / img_size) - 1
+    if bbox is not None:
+        use_cam = crop_cam
+    else:
+        cam = _host(cam)
+        cam_crop = np.hstack([proc * cam[0] * 0.5, cam[1:] + (2. / cam[0]) * 0.5])
+        cam_orig = np.hstack([cam_crop[0] * undo_scale, cam_crop[1:] + (start_pt - proc) / cam_crop[0]])
+        k = 2. / img_size
+        use_cam = np.hstack([cam_orig[0] * k, cam_orig[1:] - (1 / (k * cam_orig[0]))]).astype(np.float32)
+    return visualize_img(img=img, cam=use_cam, kp_pred=kp_orig, vert=vert, renderer=renderer, rotated_view=rotated_view,
+                         mesh_color=mesh_color, pad_vals=pad_vals, no_text=no_text)
+
+
+__all__ = ["VisRenderer", "colors", "load_faces", "visualize_img", "visualize_img_orig", "make_square", "remove_pads"]

@@ -1,13 +1,19 @@
-"""The three mesh panels of the demo's `render_preds` (src/evaluation/run_video.py:110-202) for all n frames at once:
+"""The panels of the demo's `render_preds` (src/evaluation/run_video.py:110-202) for all n frames at once:
 
     render_og  visualize_img_orig's mesh over the original frame (down-scaled to max_img_size, make_square, remove_pads)
     rot_og     the same camera, the mesh rotated 90 deg about y through its centroid, on white (VisRenderer.rotated)
     rend_crop  visualize_img's mesh over the 224x224 crop
+    skel_crop  visualize_img's 2D skeleton over the crop (view 'skel', one hmmr_draw_skeleton launch)
+    collage    | rend_crop | render_og |  (view 'collage', one hmmr_compose_collage launch over the four panels)
+               | skel_crop | rot_og    |
 
 Each panel is one hmmr_render_mesh call (three launches per 64 frames) reading cams / verts in place inside the packed
 per-frame records; the camera change to the original image is the device code of hmmr_render_handoff, so nothing
-crosses PCIe until the caller downloads the uint8 panels.  The skeleton panel, draw_text, the 2x2 collage and the PNG /
-mp4 writing need cv2 and ffmpeg and are left to the caller.
+crosses PCIe until the caller downloads uint8 frames: with views=('collage',) the finished collage frames (and, for
+render_preds' second folder, the 'orig' panel).  PNG and mp4 writing is evaluation/run_video.render_preds'; `draw_text`
+(cv2.putText) is not provided.  The skeleton's draw list is the reference's, executed; the pixels of its discs, rings and
+lines follow the integer rules of include/hmmr_hip.h, and their agreement with OpenCV's scan conversion at primitive
+boundaries has not been measured.
 """
 from __future__ import annotations
 
@@ -15,6 +21,7 @@ import numpy as np
 import torch
 
 from ... import _lib as L
+from .collage import compose_collage, skeleton_panels
 from .handoff import orig_image_geometry
 from .raster import COLORS, MeshFaces, render_mesh, rodrigues
 
@@ -41,12 +48,26 @@ def _cams_verts(records, layout, device):
     return records[:, oc:oc + sc], records[:, ov:ov + sv].unflatten(1, tuple(shp_v))
 
 
+def _kps(records, layout, device):
+    """(rows [n, >= 2 K] read in place, K)"""
+    if isinstance(records, dict):
+        k = records["kps"]
+        k = torch.as_tensor(np.asarray(k, np.float32) if not torch.is_tensor(k) else k, device=device).float()
+        return k.reshape(k.shape[0], -1), int(k.shape[1])
+    ok, sk, shp = {k: (off, size, shp) for k, shp, off, size in layout}["kps"]
+    return records[:, ok:ok + sk], int(shp[0])
+
+
 def render_views(records, layout, frames_uint8, image_og_params, faces, crops=None, views=('orig', 'rotated', 'crop'),
                  max_img_size=720, mesh_color='blue', device=None):
     """records [n, rec_len] packed per-frame records (Tester.predict_records, dist.record_layout) or the dict of
     predict_all_images; frames_uint8 [n,H,W,3] original frames; image_og_params: n dicts of process_image (start_pt,
     scale, im_shape); faces [F,3] (or a MeshFaces); crops [n,224,224,3] in [-1, 1] for the crop panel.
-    -> {'orig': uint8 [n,h',w',3], 'rotated': uint8 [n,h',w',3], 'crop': uint8 [n,224,224,3]} on the device."""
+    -> {'orig': uint8 [n,h',w',3], 'rotated': uint8 [n,h',w',3], 'crop': uint8 [n,224,224,3]} on the device.
+    Further view names: 'skel' uint8 [n,224,224,3], the predicted 2D skeleton over the crop, and 'collage' uint8
+    [n, 448, 224 + max(w' 224 // h', 224), 3], render_preds' frame, which implies (and returns) the other four."""
+    if 'collage' in views:
+        views = tuple(views) + ('orig', 'rotated', 'crop', 'skel')
     if device is None:
         device = records.device if torch.is_tensor(records) else torch.device("cuda", torch.cuda.current_device())
     faces = faces if isinstance(faces, MeshFaces) else MeshFaces(faces)
@@ -70,4 +91,12 @@ def render_views(records, layout, frames_uint8, image_og_params, faces, crops=No
         cr = torch.as_tensor(crops, device=device).float()
         out['crop'] = render_mesh(verts, cams, faces, cr.shape[1], color=color, bg_mode=L.RENDER_BG_FLOAT, bg_image=cr,
                                   bg_add=1.0, bg_mul=127.5)["rgb"]
+    if 'skel' in views:
+        if crops is None:
+            raise ValueError("the skeleton panel needs the 224x224 crops")
+        cr = torch.as_tensor(crops, device=device).float()
+        rows, nk = _kps(records, layout, device)             # ((kp + 1) * 0.5) * img_size and ((img + 1) * 0.5) * 255, fused
+        out['skel'] = skeleton_panels(rows, cr, nk=nk, kp_add=1.0, kp_mul=0.5 * cr.shape[1], bg_add=1.0, bg_mul=127.5)
+    if 'collage' in views:
+        out['collage'] = compose_collage(out['crop'], out['skel'], out['orig'], out['rotated'])
     return out

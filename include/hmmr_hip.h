@@ -634,6 +634,64 @@ size_t hmmr_render_workspace_bytes(int n, int nv, int nf);
 int hmmr_render_mesh(const hmmr_render_desc_t* d, void* stream);
 
 /* ------------------------------------------------------------------------- *
+ * The skeleton panel and the 2x2 collage of the demo (csrc/collage.hip; additive to ABI 19).
+ *
+ * hmmr_draw_skeleton replaces draw_skeleton (src/util/render/render_utils.py:38-234) as visualize_img calls it
+ * (src/util/render/nmr_renderer.py:303-316), for n frames per launch.  The DRAW LIST is the reference's: per child, in
+ * index order, a white disc of radius r, the child's disc of radius r - 1, the parent's disc of radius r - 1 and a line of
+ * thickness r - 2 in the edge colour; an invisible child is skipped, an invisible parent suppresses its disc and the line;
+ * draw_edges = 0 draws a 1-pixel ring of radius r - 1 per visible joint and nothing else; parents and colours for 19 and
+ * 25 joints.  The PIXELS of a primitive are specified here, in exact integer arithmetic (centres and end points are
+ * integers, dx, dy run from the pixel to the centre), because OpenCV's scan conversion could not be recorded:
+ *   disc(c, r)       dx dx + dy dy <= r r + r
+ *   ring(c, r)       disc(c, r) minus disc(c, r - 1)
+ *   line(p0, p1, t)  4 dist^2(q, segment) <= t t: with d = p1 - p0, L = d.d, s = clamp((q - p0).d, 0, L),
+ *                    4 |(q - p0) L - s d|^2 <= t t L L; for L = 0, 4 |q - p0|^2 <= t t (a capsule with round caps)
+ * Agreement with cv2.circle / cv2.line at the boundary pixels of a primitive has NOT been measured.
+ *   joints      (kp + kp_add) * kp_mul in fp32 (kp_add = 1, kp_mul = img_size / 2: the bits of ((kp + 1) * 0.5) * img_size),
+ *               rounded half to even, then clamped to [-32768, 32767] (a deviation: the reference keeps any integer);
+ *               a joint with a NaN coordinate counts as invisible.
+ *   radius      0: max(4, int(mean(h, w) * 0.01)) (hmmr_skeleton_radius); with draw_edges, a radius < 3 is refused (the line's
+ *               thickness would be < 1, where OpenCV asserts).
+ *   background  bg_float [n][h][w][3]: trunc(clamp((img + bg_add) * bg_mul, 0, 255)) where no primitive covers the pixel (the
+ *               astype(uint8) of a float image), or bg_u8 [n][h][w][3], which may be `out` itself (drawn in place).
+ * ------------------------------------------------------------------------- */
+#define HMMR_SKELETON_MAX_RADIUS 1024
+typedef struct {
+    const float* kps; int64_t ld_kps;         /* [n] rows of >= 2 nk floats: x0 y0 x1 y1 ... (e.g. the kps field of packed records) */
+    const unsigned char* vis;                 /* NULL, or [n][nk]: 0 = invisible */
+    int n, nk, h, w;                          /* frames, joints (19 or 25), image rows and columns (as hmmr_render_mesh's size) */
+    float kp_add, kp_mul;
+    int draw_edges;                           /* 0 or 1 */
+    int radius;                               /* 0: the reference's rule */
+    const float* bg_float; float bg_add, bg_mul;
+    const unsigned char* bg_u8;               /* exactly one of bg_float / bg_u8 */
+    unsigned char* out;                       /* [n][h][w][3] */
+} hmmr_skeleton_desc_t;
+int hmmr_skeleton_radius(int h, int w);       /* the reference's radius for an h x w image (0: bad arguments) */
+int hmmr_draw_skeleton(const hmmr_skeleton_desc_t* d, void* stream);
+
+/* hmmr_compose_collage replaces the tail of render_preds (src/evaluation/run_video.py:178-197) for n frames per launch:
+ *     | rend_crop | render_og resized to (w', S) |        w' = w S / h (integer division)
+ *     | skel_crop | rot_og resized to (S, S)     |        the narrower right panel padded with ones on its right
+ * Panels are uint8; the reference's floats are restated: value / 255 (float32 for the skeleton panel), cv2.resize's
+ * INTER_LINEAR as hmmr_img::taps has it (fp64, horizontal pass first), padding 1.0, and plt.imsave's trunc(x 255).
+ * out [n][2 S][hmmr_collage_width(S, h, w)][3]. */
+#define HMMR_COLLAGE_MAX_PANEL_WIDTH 4096
+typedef struct {
+    const unsigned char* rend_crop;           /* [n][S][S][3] */
+    const unsigned char* skel_crop;           /* [n][S][S][3] */
+    const unsigned char* render_og;           /* [n][h][w][3] */
+    const unsigned char* rot_og;              /* [n][h][w][3] */
+    int n, S, h, w;
+    unsigned char* out;
+} hmmr_collage_desc_t;
+/* S + max(w', S); 0 for S outside hmmr_render_mesh's sizes, h or w outside [1, HMMR_RENDER_MAX_SIZE], or w' outside
+ * [1, HMMR_COLLAGE_MAX_PANEL_WIDTH] */
+int hmmr_collage_width(int S, int h, int w);
+int hmmr_compose_collage(const hmmr_collage_desc_t* d, void* stream);
+
+/* ------------------------------------------------------------------------- *
  * Evaluation metrics on device (src/evaluation/eval_util.py): per-frame MPJPE after pelvis alignment
  * and after Procrustes alignment (compute_error_3d :30-60 with align_by_pelvis :158 and
  * compute_similarity_transform :177), acceleration (compute_accel :14) and acceleration error
