@@ -92,6 +92,25 @@ class ResnetWeights(C.Structure):
                 ("unit", ResnetUnit * RESNET_UNITS), ("post_scale", _fp), ("post_shift", _fp)]
 
 
+SC_NONE, SC_LAUNCH, SC_LAUNCH_WITH_CONV1, SC_IN_CONV3, SC_IN_TAIL = range(5)
+CONV1_LAUNCH, CONV1_READY = range(2)
+CONV2_LAUNCH, CONV2_IN_TAIL = range(2)
+END_CONV3_LAUNCH, END_TAIL_BF16, END_TAIL_BF16_STRIDE2, END_TAIL_SPLIT, END_B1_UNIT, END_UNIT_PAIR = range(6)
+
+
+class UnitPlan(C.Structure):
+    """hmmr_unit_plan_t: what hmmr_resnet50_fwd launches for one unit (hmmr_resnet50_plan; host only)"""
+    _fields_ = [(k, C.c_int) for k in ("shortcut", "conv1", "conv2", "end", "reads_fused_preact", "writes_raw", "writes_pre",
+                                       "pair_demoted", "swaps_t1_t2", "leaves_h1")]
+
+
+def resnet_plan(rw, n_total):
+    """[UnitPlan] * 16 for a pass of n_total frames over the packed table `rw` under the current hmmr_debug_t."""
+    plan = (UnitPlan * RESNET_UNITS)()
+    check(load().hmmr_resnet50_plan(C.byref(rw), int(n_total), plan), "hmmr_resnet50_plan")
+    return list(plan)
+
+
 class TemporalBlock(C.Structure):
     _fields_ = [("gn1_gamma", _fp), ("gn1_beta", _fp), ("conv1", Layer),
                 ("gn2_gamma", _fp), ("gn2_beta", _fp), ("conv2", Layer)]
@@ -192,6 +211,7 @@ SIGNATURES = {
     "hmmr_resnet50_workspace_bytes": (C.c_size_t, [C.c_int, C.c_int]),
     "hmmr_resnet50_fwd": (C.c_int, [C.POINTER(ResnetWeights), _fp, C.c_int, C.c_int, _fp, _vp, C.c_size_t, _vp,
                                     C.POINTER(C.c_float)]),
+    "hmmr_resnet50_plan": (C.c_int, [C.POINTER(ResnetWeights), C.c_int, C.POINTER(UnitPlan)]),
     "hmmr_temporal_workspace_bytes": (C.c_size_t, [C.c_int, C.c_int, C.c_int]),
     "hmmr_temporal_fwd": (C.c_int, [C.POINTER(TemporalWeights), _fp, C.c_int, C.c_int, _fp, _vp, C.c_size_t, _vp]),
     "hmmr_hallucinator_workspace_bytes": (C.c_size_t, [C.c_int, C.c_int]),

@@ -198,10 +198,132 @@ extern "C" size_t hmmr_resnet50_workspace_bytes(int n, int dtype) {
     return n > 0 ? resnet_layout(n, dtype).total : 0;
 }
 
+// ------------------------------------------------------------------------- //
+// The schedule of a pass is a VALUE: hmmr_resnet50_plan decides what every unit launches (plan_unit: a pure host function
+// that holds every structural check), resnet_fwd_t then issues the 16 plans in order.
+static bool stem_unfused(const hmmr_resnet_weights_t* w, const hmmr_debug_t* dbg) {
+    return dbg->stem_route == 1 || (dbg->stem_route == 0 && w->dtype == HMMR_F32);
+}
+// the fused stem computes block1/unit_1's conv1 on each pooled tile inside the same launch (-> T1): bf16, and f16x3 with the
+// fragment-major copy of the conv1 filters (hmmr_resnet_unit_t.conv1_frag, round 5)
+static bool stem_writes_conv1(const hmmr_resnet_weights_t* w, const hmmr_debug_t* dbg) {
+    const hmmr_resnet_unit_t& U0 = w->unit[0];
+    return !stem_unfused(w, dbg) && !dbg->stem_no_conv1 && (w->dtype == HMMR_BF16 || (w->dtype == HMMR_F16X3 && U0.conv1_frag)) &&
+           !U0.sc_c1.w && U0.c_in == 64 && U0.base == 64 && U0.conv1.scale && U0.conv1.shift;
+}
+
+// Unit u on n images of H x H pixels.  have_raw / h1_ready: what the previous unit (the stem) left behind -- the raw trunk of this
+// unit's input, this unit's conv1 output in T1.
+// A unit's pre-activation BN + ReLU (`preact`) reaches its 1x1 consumers (conv1 and the conv shortcut) as `fuse_preact` says:
+//   1: they read the RAW trunk and apply the preact while staging their A operand (the tensor never exists in HBM);
+//   0: the previous unit's conv3 epilogue writes it as a second output (the consumers keep the pure LDS-DMA operand path).
+// Measured at batch 256 (bf16): fusing blocks 1-2 cuts the ResNet pass by 4.5 %, blocks 3-4 are neutral; the packer enables it everywhere.
+static int plan_unit(const hmmr_resnet_weights_t* w, int u, int n, int H, const hmmr_debug_t* dbg, bool have_raw, bool h1_ready,
+                     hmmr_unit_plan_t* out) {
+    const hmmr_resnet_unit_t& U = w->unit[u];
+    const int Ho = H / U.stride;
+    const bool last = (u == HMMR_RESNET_UNITS - 1);
+    hmmr_unit_plan_t p = {};
+    const bool fused = p.reads_fused_preact = u > 0 && U.fuse_preact;
+    HMMR_REQUIRE(!fused || (U.pre_scale && U.pre_shift && have_raw), "resnet: unit %d cannot fuse its preact", u);
+    HMMR_REQUIRE(U.shortcut.w || have_raw, "resnet: unit %d has no raw input for its identity shortcut", u);
+    // what the NEXT unit needs from this one
+    const bool next_fused = !last && w->unit[u + 1].fuse_preact;
+    const bool next_identity = !last && !w->unit[u + 1].shortcut.w;
+    p.writes_raw = last || next_fused || next_identity;
+    p.writes_pre = !last && !next_fused;
+    // a register-resident unit pair (csrc/unit_pair.hip) is one round of 128-pixel workgroups with a ~20 k-cycle prologue however few
+    // pixels there are: below ~12 k pixels (61 frames in block 3) the two launches it replaces are faster (profiles/r04_unit_pair_check.log:
+    // 0.064 against 0.096 ms at 33 frames), and they produce the same bits, so a short batch simply takes them
+    // (hmmr_debug_t.pair_min_pixels moves the switch: tests run one batch on either side of it)
+    // round 6 (profiles/r06e_pair_ws_check.log): in block 3 the two launches still win at 12 544 pixels (64 frames, FeatureExtractor's batch:
+    // 0.085 against 0.093 ms) -- its switch is at 14 000; a block-2 pair is a shorter tile and wins from ~12 000 (0.034 against 0.043 ms at 15 680)
+    const long long pair_min = dbg->pair_min_pixels > 0 ? dbg->pair_min_pixels : (U.base >= 256 ? 14000 : 12000);
+    p.pair_demoted = w->dtype == HMMR_F16X3 && U.pair_stream && U.fuse_tail == 1 && (long long)n * Ho * Ho < pair_min;
+    const int fuse_tail = p.pair_demoted ? 0 : U.fuse_tail;
+    // the conv shortcut folded into conv3: ONE GEMM over {h2, preact} with [W3 | Wsc] (hmmr_conv_desc_t.in2);
+    // the shortcut tensor (the widest tensor of the unit) is neither written nor read back
+    HMMR_REQUIRE(!U.c3sc.w || (U.shortcut.w && !fused && U.stride == 1 && fuse_tail <= 2 && !U.sc_c1.w),
+                 "resnet: unit %d cannot fold its shortcut into conv3", u);
+    if (U.c3sc.w) {
+        p.shortcut = HMMR_SC_IN_CONV3;
+    } else if (fuse_tail == 3) {
+        HMMR_REQUIRE(U.shortcut.w && !U.shortcut.scale && !fused && U.c_in == 64 && U.stride == 1,
+                     "resnet: unit %d cannot compute its shortcut inside the tail", u);
+        p.shortcut = HMMR_SC_IN_TAIL;
+    } else if (U.shortcut.w) {
+        p.shortcut = (U.sc_c1.w && !h1_ready && U.stride == 1) ? HMMR_SC_LAUNCH_WITH_CONV1 : HMMR_SC_LAUNCH;
+    }
+    p.conv1 = (h1_ready || p.shortcut == HMMR_SC_LAUNCH_WITH_CONV1) ? HMMR_CONV1_READY : HMMR_CONV1_LAUNCH;
+    p.conv2 = fuse_tail >= 2 ? HMMR_CONV2_IN_TAIL : HMMR_CONV2_LAUNCH;       // (4: the single-phase tail of a stride-2 unit)
+    HMMR_REQUIRE(!p.writes_pre || (w->unit[u + 1].pre_scale && w->unit[u + 1].pre_shift), "resnet: unit %d lacks its preact BN", u + 1);
+    if (fuse_tail == 4) {             // stride-2 last unit of a block: conv2 + conv3 + add in one launch, no next conv1
+        HMMR_REQUIRE(!last && w->dtype == HMMR_BF16 && U.conv2.scale && U.conv2.shift && !U.shortcut.w &&
+                     ((U.base == 64 && U.depth == 256) || (U.base == 128 && U.depth == 512)),
+                     "resnet: unit %d cannot run as a single-phase tail", u);
+        p.end = HMMR_END_TAIL_BF16_STRIDE2;
+    } else if (fuse_tail) {           // conv3 + add + the next unit's preact + conv1 in one launch
+        const bool pair = w->dtype == HMMR_F16X3 && U.pair_stream && fuse_tail == 1;
+        HMMR_REQUIRE(!last && (w->dtype == HMMR_BF16 || pair || (w->dtype == HMMR_F16X3 && ((U.w3_frag && U.w1n_frag) || U.unit_stream) && fuse_tail <= 2)) &&
+                     U.stride == 1 && p.writes_raw && !p.writes_pre && next_fused &&
+                     next_identity && w->unit[u + 1].base == U.base && w->unit[u + 1].c_in == U.depth &&
+                     ((U.base == 64 && U.depth == 256) || (U.base == 128 && U.depth == 512) || (pair && U.base == 256 && U.depth == 1024)),
+                     "resnet: unit %d cannot fuse its tail", u);
+        if (p.conv2 == HMMR_CONV2_IN_TAIL) {
+            HMMR_REQUIRE(U.conv2.scale && U.conv2.shift, "resnet: unit %d cannot fuse its conv2", u);
+            HMMR_REQUIRE((U.conv2.k_order == 2) == (w->dtype == HMMR_F16X3 && U.unit_stream != nullptr),
+                         "resnet: unit %d: a k_order 2 conv2 runs inside the unit only as part of its unit_stream (csrc/b1_unit.hip)", u);
+            p.swaps_t1_t2 = 1;        // h2 never exists in HBM; conv1' goes to T2 (neighbouring tiles' halos still read T1), then the two swap roles
+        }
+        p.end = w->dtype == HMMR_BF16 ? HMMR_END_TAIL_BF16 : pair ? HMMR_END_UNIT_PAIR :
+                (p.swaps_t1_t2 && U.unit_stream) ? HMMR_END_B1_UNIT : HMMR_END_TAIL_SPLIT;
+        p.leaves_h1 = 1;
+    }
+    *out = p;
+    return 0;
+}
+
+extern "C" int hmmr_resnet50_plan(const hmmr_resnet_weights_t* w, int n_total, hmmr_unit_plan_t out[HMMR_RESNET_UNITS]) {
+    HMMR_REQUIRE(w && out && n_total > 0, "hmmr_resnet50_plan: null argument or no image");
+    const hmmr_debug_t* dbg = hmmr_debug_state();
+    int H = 56;
+    bool have_raw = false, h1_ready = stem_writes_conv1(w, dbg);
+    for (int u = 0; u < HMMR_RESNET_UNITS; ++u) {
+        if (plan_unit(w, u, n_total, H, dbg, have_raw, h1_ready, &out[u])) return -1;
+        have_raw = out[u].writes_raw; h1_ready = out[u].leaves_h1; H /= w->unit[u].stride;
+    }
+    return 0;
+}
+
+// a k x k convolution (stride, pad k / 2) of layer L over the dense NHWC tensor in [n][H][H][cin] -> out [n][H / stride][H / stride][cout]
+static hmmr_conv_desc_t dense_conv(int dtype, int n, const void* in, int H, int cin, int k, int stride, int cout, const hmmr_layer_t& L,
+                                   void* out) {
+    hmmr_conv_desc_t d = {};
+    d.in = in; d.w = L.w; d.scale = L.scale; d.shift = L.shift; d.tile = L.tile; d.k_order = L.k_order;
+    d.out = out; d.in_dtype = d.out_dtype = dtype;
+    d.n_img = n; d.hin = d.win = H; d.cin = cin;
+    d.in_img_stride = (int64_t)H * H * cin; d.in_row_stride = H * cin; d.in_px_stride = cin;
+    d.kh = d.kw = k; d.sy = d.sx = stride; d.py = d.px = k / 2; d.ho = d.wo = H / stride; d.cout = d.ldo = cout;
+    return d;
+}
+
+// the other operand of a unit's add (hmmr_conv_desc_t or hmmr_tail_desc_t): rows of `depth` elements, or -- stride > 1 --
+// max_pool2d(x, [1,1], stride) = x[:, ::s, ::s] of the NHWC tensor x [.][H][H][depth]
+template <typename D>
+static void set_residual(D& d, const void* x, int depth, int H, int stride) {
+    d.res = x;
+    if (stride == 1) { d.ldr = depth; return; }
+    d.res_strided = 1;
+    d.res_img_stride = (int64_t)H * H * depth; d.res_row_stride = stride * H * depth; d.res_px_stride = stride * depth;
+}
+
 template <typename T>
 static int resnet_fwd_t(const hmmr_resnet_weights_t* w, const float* images, int n_real, int n, float* phi,
                         char* ws, hipStream_t s, float* prof_ms) {
-    const ResnetBufs L = resnet_layout(n, w->dtype);
+    hmmr_unit_plan_t plan[HMMR_RESNET_UNITS];
+    if (hmmr_resnet50_plan(w, n, plan)) return -1;       // (nothing has been launched yet)
+    const int dt = w->dtype;
+    const ResnetBufs L = resnet_layout(n, dt);
     T* xpad = (T*)(ws + L.xpad);
     T* stem = (T*)(ws + L.stem);
     T* X[2] = {(T*)(ws + L.x[0]), (T*)(ws + L.x[1])};
@@ -218,16 +340,11 @@ static int resnet_fwd_t(const hmmr_resnet_weights_t* w, const float* images, int
     // ~1 % slower than the three-kernel route, which therefore stays the fp32 default.  f16x3 has its own
     // fused kernel (stem_fused_split_kernel: hi/lo planes, 32 output channels per workgroup).
     const hmmr_debug_t* dbg = hmmr_debug_state();
-    const bool unfused = dbg->stem_route == 1 || (dbg->stem_route == 0 && w->dtype == HMMR_F32);
-    bool stem_c1 = false;
-    if (!unfused) {
-        // bf16: block1/unit_1's conv1 is computed on each pooled tile inside the same launch (-> T1)
-        const hmmr_resnet_unit_t& U0 = w->unit[0];
-        // (f16x3, round 5: with the fragment-major copy of the conv1 filters, hmmr_resnet_unit_t.conv1_frag)
-        stem_c1 = !dbg->stem_no_conv1 && (w->dtype == HMMR_BF16 || (w->dtype == HMMR_F16X3 && U0.conv1_frag)) && !U0.sc_c1.w && U0.c_in == 64 &&
-                  U0.base == 64 && U0.conv1.scale && U0.conv1.shift;
-        if (hmmr_stem_fused(images, n_real, n, w->stem.w, w->stem.scale, w->stem.shift, U0.pre_scale, U0.pre_shift, P[0], w->dtype, s,
-                            stem_c1 ? (w->dtype == HMMR_F16X3 ? U0.conv1_frag : U0.conv1.w) : nullptr, U0.conv1.scale, U0.conv1.shift,
+    const hmmr_resnet_unit_t& U0 = w->unit[0];
+    if (!stem_unfused(w, dbg)) {
+        const bool stem_c1 = stem_writes_conv1(w, dbg);
+        if (hmmr_stem_fused(images, n_real, n, w->stem.w, w->stem.scale, w->stem.shift, U0.pre_scale, U0.pre_shift, P[0], dt, s,
+                            stem_c1 ? (dt == HMMR_F16X3 ? U0.conv1_frag : U0.conv1.w) : nullptr, U0.conv1.scale, U0.conv1.shift,
                             stem_c1 ? T1 : nullptr))
             return -2;
         if (prof_mark(pf)) return -2;
@@ -244,7 +361,7 @@ static int resnet_fwd_t(const hmmr_resnet_weights_t* w, const float* images, int
         if (prof_mark(pf)) return -2;
         hmmr_conv_desc_t d = {};
         d.in = xpad; d.w = w->stem.w; d.scale = w->stem.scale; d.shift = w->stem.shift;
-        d.out = stem; d.in_dtype = d.out_dtype = w->dtype;
+        d.out = stem; d.in_dtype = d.out_dtype = dt;
         d.n_img = n; d.hin = PADH; d.win = 2 * 111 + 1; d.cin = 32;
         d.in_img_stride = (int64_t)PADH * PADW * 4; d.in_row_stride = PADW * 4; d.in_px_stride = 4;
         d.kh = 8; d.kw = 1; d.sy = 2; d.sx = 2; d.py = 0; d.px = 0;
@@ -253,197 +370,97 @@ static int resnet_fwd_t(const hmmr_resnet_weights_t* w, const float* images, int
         if (prof_mark(pf)) return -2;
         const long long nvec = (long long)n * 56 * 56 * 8;
         const int g2 = (int)((nvec + 255) / 256 < 16384 ? (nvec + 255) / 256 : 16384);
-        hipLaunchKernelGGL(maxpool_bn_relu_kernel<T>, dim3(g2), dim3(256), 0, s, (const T*)stem, P[0],
-                           w->unit[0].pre_scale, w->unit[0].pre_shift, nvec);
+        hipLaunchKernelGGL(maxpool_bn_relu_kernel<T>, dim3(g2), dim3(256), 0, s, (const T*)stem, P[0], U0.pre_scale, U0.pre_shift, nvec);
         HMMR_CHECK_HIP(hipGetLastError());
         if (prof_mark(pf)) return -2;
     }
 
-    // Units.  A unit's pre-activation BN + ReLU (`preact`) reaches its 1x1 consumers (conv1 and the
-    // conv shortcut) in one of two ways, chosen per unit by `fuse_preact`:
-    //   1: the consumers read the RAW trunk and apply the preact while staging their A operand
-    //      (the tensor never exists in HBM; pays in the HBM-bound early blocks);
-    //   0: the previous unit's conv3 epilogue writes it as a second output (the consumers keep the
-    //      pure LDS-DMA operand path; better for the MFMA-bound late blocks).
-    // Measured at batch 256 (bf16): fusing blocks 1-2 cuts the ResNet pass by 4.5 %, blocks 3-4 are
-    // neutral; the packer enables it everywhere.
+    // ---- units.  X[cur]: the raw trunk, P[pcur]: its pre-activated form (each where the plan has it written), T1 / T2: conv1's and
+    // conv2's outputs.  Every layer owns one profile slot per pass -- [shortcut] conv1 conv2 conv3 -- whether or not the plan gives it a
+    // launch of its own: the mark after each step below is that slot.
     int H = 56, cur = 0, pcur = 0;
-    bool have_raw = false;            // X[cur] holds the raw input of the unit
-    bool h1_ready = stem_c1;          // T1 already holds this unit's conv1 output (previous unit's fused tail / the stem)
     for (int u = 0; u < HMMR_RESNET_UNITS; ++u) {
         const hmmr_resnet_unit_t& U = w->unit[u];
+        const hmmr_resnet_unit_t& N = w->unit[u + 1 < HMMR_RESNET_UNITS ? u + 1 : u];     // (read only where the plan has a next unit)
+        const hmmr_unit_plan_t& p = plan[u];
         const int Ho = H / U.stride;
-        const bool last = (u == HMMR_RESNET_UNITS - 1);
-        const bool fused = u > 0 && U.fuse_preact;
-        const T* xin = fused ? (const T*)X[cur] : (const T*)P[pcur];
-        const float* ps = fused ? U.pre_scale : nullptr;
-        const float* pb = fused ? U.pre_shift : nullptr;
-        HMMR_REQUIRE(!fused || (ps && pb && have_raw), "resnet: unit %d cannot fuse its preact", u);
-        const bool identity = !U.shortcut.w;
-        HMMR_REQUIRE(!identity || have_raw, "resnet: unit %d has no raw input for its identity shortcut", u);
-        // what the NEXT unit needs from this one
-        const bool next_fused = !last && w->unit[u + 1].fuse_preact;
-        const bool next_identity = !last && !w->unit[u + 1].shortcut.w;
-        const bool write_raw = last || next_fused || next_identity;
-        const bool write_pre = !last && !next_fused;
+        const T* xin = p.reads_fused_preact ? (const T*)X[cur] : (const T*)P[pcur];
+        const float* ps = p.reads_fused_preact ? U.pre_scale : nullptr;
+        const float* pb = p.reads_fused_preact ? U.pre_shift : nullptr;
         T* xn = X[cur ^ 1];
-        T* pn = P[pcur ^ 1];
+        T* out = p.writes_raw ? xn : nullptr;
+        T* pre = p.writes_pre ? P[pcur ^ 1] : nullptr;
+        const bool sc_in_c3 = p.shortcut == HMMR_SC_IN_CONV3;
+        // the add reads the unit's raw input (subsampled by the unit's stride) or the shortcut launch's output (xn, overwritten in place)
+        const T* res = p.shortcut == HMMR_SC_NONE ? X[cur] : xn;
+        const int res_stride = p.shortcut == HMMR_SC_NONE ? U.stride : 1;
         hmmr_conv_desc_t d;
-        const bool sc_c1 = U.shortcut.w && U.sc_c1.w && !h1_ready && U.stride == 1;
-        // a register-resident unit pair (csrc/unit_pair.hip) is one round of 128-pixel workgroups with a ~20 k-cycle prologue however few
-        // pixels there are: below ~12 k pixels (61 frames in block 3) the two launches it replaces are faster (profiles/r04_unit_pair_check.log:
-        // 0.064 against 0.096 ms at 33 frames), and they produce the same bits, so a short batch simply takes them
-        // (hmmr_debug_t.pair_min_pixels moves the switch: tests run one batch on either side of it)
-        // round 6 (profiles/r06e_pair_ws_check.log): in block 3 the two launches still win at 12 544 pixels (64 frames, FeatureExtractor's batch:
-        // 0.085 against 0.093 ms) -- its switch is at 14 000; a block-2 pair is a shorter tile and wins from ~12 000 (0.034 against 0.043 ms at 15 680)
-        const long long pair_min = dbg->pair_min_pixels > 0 ? dbg->pair_min_pixels : (U.base >= 256 ? 14000 : 12000);
-        const bool pair_off = w->dtype == HMMR_F16X3 && U.pair_stream && U.fuse_tail == 1 && (long long)n * Ho * Ho < pair_min;
-        const int fuse_tail = pair_off ? 0 : U.fuse_tail;
-        const bool sc_in_tail = fuse_tail == 3;          // the conv shortcut is computed inside the fused tail
-        // the conv shortcut is folded into conv3: ONE GEMM over {h2, preact} with [W3 | Wsc] (hmmr_conv_desc_t.in2);
-        // the shortcut tensor (the widest tensor of the unit) is neither written nor read back
-        const bool sc_in_c3 = U.c3sc.w != nullptr;
-        HMMR_REQUIRE(!sc_in_c3 || (U.shortcut.w && !fused && U.stride == 1 && fuse_tail <= 2 && !U.sc_c1.w),
-                     "resnet: unit %d cannot fold its shortcut into conv3", u);
-        if (sc_in_c3) {
-            if (prof_mark(pf)) return -2;
-        } else if (sc_in_tail) {
-            HMMR_REQUIRE(U.shortcut.w && !U.shortcut.scale && !fused && U.c_in == 64 && U.stride == 1,
-                         "resnet: unit %d cannot compute its shortcut inside the tail", u);
-            if (prof_mark(pf)) return -2;
-        } else if (U.shortcut.w) {    // 1x1 conv on preact, bias, no BN/ReLU (stride is 1 here)
-            d = hmmr_conv_desc_t{};
-            d.in = xin; d.pro_scale = ps; d.pro_shift = pb;
-            d.w = U.shortcut.w; d.scale = U.shortcut.scale; d.shift = U.shortcut.shift; d.tile = U.shortcut.tile;
-            d.out = xn; d.in_dtype = d.out_dtype = w->dtype;
-            d.n_img = n; d.hin = H; d.win = H; d.cin = U.c_in;
-            d.in_img_stride = (int64_t)H * H * U.c_in; d.in_row_stride = H * U.c_in; d.in_px_stride = U.c_in;
-            d.kh = d.kw = 1; d.sy = d.sx = U.stride; d.ho = d.wo = Ho; d.cout = U.depth; d.ldo = U.depth;
-            if (sc_c1) {              // ... and conv1 over the same operand as extra output columns (-> T1, BN + ReLU)
+        if (p.shortcut == HMMR_SC_LAUNCH || p.shortcut == HMMR_SC_LAUNCH_WITH_CONV1) {   // 1x1 conv on preact, bias, no BN/ReLU
+            d = dense_conv(dt, n, xin, H, U.c_in, 1, U.stride, U.depth, U.shortcut, xn);
+            d.pro_scale = ps; d.pro_shift = pb;
+            d.k_order = 0;            // (shortcut.k_order only names the tile family of the sc_c1 launch: HmmrEngine._tile_for)
+            if (p.shortcut == HMMR_SC_LAUNCH_WITH_CONV1) {   // ... and conv1 over the same operand as extra output columns (-> T1, BN + ReLU)
                 d.w = U.sc_c1.w; d.scale = U.sc_c1.scale; d.shift = U.sc_c1.shift; d.k_order = U.sc_c1.k_order;
                 d.cout = U.depth + U.base; d.out_b = T1; d.ldo_b = U.base; d.n_split = U.depth; d.relu_b = 1;
             }
             if (hmmr_conv_gemm(&d, s)) return -2;
-            if (prof_mark(pf)) return -2;
-            if (sc_c1) h1_ready = true;
         }
-        // conv1: 1x1 on preact, BN + ReLU (already in T1 if the previous unit ended in a fused tail)
-        if (!h1_ready) {
-            d = hmmr_conv_desc_t{};
-            d.in = xin; d.pro_scale = ps; d.pro_shift = pb;
-            d.w = U.conv1.w; d.scale = U.conv1.scale; d.shift = U.conv1.shift; d.relu = 1; d.tile = U.conv1.tile;
-            d.k_order = U.conv1.k_order;      // (2: the two-ring stream kernel of csrc/conv1x1_stream.hip; it takes the pre-activated tensor)
-            d.out = T1; d.in_dtype = d.out_dtype = w->dtype;
-            d.n_img = n; d.hin = H; d.win = H; d.cin = U.c_in;
-            d.in_img_stride = (int64_t)H * H * U.c_in; d.in_row_stride = H * U.c_in; d.in_px_stride = U.c_in;
-            d.kh = d.kw = 1; d.sy = d.sx = 1; d.ho = d.wo = H; d.cout = U.base; d.ldo = U.base;
+        if (p.shortcut != HMMR_SC_NONE && prof_mark(pf)) return -2;
+        if (p.conv1 == HMMR_CONV1_LAUNCH) {   // 1x1 on preact, BN + ReLU (k_order 2: the two-ring stream kernel of csrc/conv1x1_stream.hip; it takes the pre-activated tensor)
+            d = dense_conv(dt, n, xin, H, U.c_in, 1, 1, U.base, U.conv1, T1);
+            d.pro_scale = ps; d.pro_shift = pb; d.relu = 1;
             if (hmmr_conv_gemm(&d, s)) return -2;
         }
         if (prof_mark(pf)) return -2;
-        // conv2: 3x3 conv2d_same(stride): pad 1/1 both for stride 1 (SAME) and stride 2 (explicit pad + VALID);
-        // with fuse_tail == 2 it runs inside the fused tail below
-        const bool conv2_in_tail = fuse_tail >= 2;       // (4: the single-phase tail of a stride-2 unit)
-        if (!conv2_in_tail) {
-            d = hmmr_conv_desc_t{};
-            d.in = T1; d.w = U.conv2.w; d.scale = U.conv2.scale; d.shift = U.conv2.shift; d.relu = 1; d.tile = U.conv2.tile;
-            d.k_order = U.conv2.k_order;
-            d.out = T2; d.in_dtype = d.out_dtype = w->dtype;
-            d.n_img = n; d.hin = H; d.win = H; d.cin = U.base;
-            d.in_img_stride = (int64_t)H * H * U.base; d.in_row_stride = H * U.base; d.in_px_stride = U.base;
-            d.kh = d.kw = 3; d.sy = d.sx = U.stride; d.py = d.px = 1; d.ho = d.wo = Ho; d.cout = U.base; d.ldo = U.base;
+        if (p.conv2 == HMMR_CONV2_LAUNCH) {   // 3x3 conv2d_same(stride): pad 1/1 both for stride 1 (SAME) and stride 2 (explicit pad + VALID)
+            d = dense_conv(dt, n, T1, H, U.base, 3, U.stride, U.base, U.conv2, T2);
+            d.relu = 1;
             if (hmmr_conv_gemm(&d, s)) return -2;
         }
         if (prof_mark(pf)) return -2;
-        // conv3: 1x1 + bias, + shortcut (no ReLU after the add)
-        d = hmmr_conv_desc_t{};
-        d.in = T2; d.w = U.conv3.w; d.scale = U.conv3.scale; d.shift = U.conv3.shift; d.tile = U.conv3.tile;
-        d.in_dtype = d.out_dtype = w->dtype;
-        d.n_img = n; d.hin = Ho; d.win = Ho; d.cin = U.base;
-        d.in_img_stride = (int64_t)Ho * Ho * U.base; d.in_row_stride = Ho * U.base; d.in_px_stride = U.base;
-        d.kh = d.kw = 1; d.sy = d.sx = 1; d.ho = d.wo = Ho; d.cout = U.depth; d.ldo = U.depth;
-        d.k_order = U.conv3.k_order;         // (2: the conv3 form of csrc/conv1x1_stream.hip, block 4)
-        if (sc_in_c3) { d.w = U.c3sc.w; d.scale = U.c3sc.scale; d.shift = U.c3sc.shift; d.tile = U.c3sc.tile; d.k_order = U.c3sc.k_order; d.in2 = xin; d.cin2 = U.c_in; }
-        else if (U.shortcut.w) { d.res = xn; d.ldr = U.depth; }
-        else if (U.stride == 1) { d.res = X[cur]; d.ldr = U.depth; }
-        else {                        // max_pool2d(x, [1,1], stride) = x[:, ::s, ::s] of the RAW input
-            d.res = X[cur]; d.res_strided = 1;
-            d.res_img_stride = (int64_t)H * H * U.depth; d.res_row_stride = U.stride * H * U.depth;
-            d.res_px_stride = U.stride * U.depth;
-        }
-        d.out = write_raw ? xn : nullptr;
-        if (write_pre) {
-            d.out2 = pn; d.scale2 = w->unit[u + 1].pre_scale; d.shift2 = w->unit[u + 1].pre_shift;
-            HMMR_REQUIRE(d.scale2 && d.shift2, "resnet: unit %d lacks its preact BN", u + 1);
-        }
-        h1_ready = false;
-        if (fuse_tail == 4) {         // stride-2 last unit of a block: conv2 + conv3 + add in one launch, no next conv1
-            HMMR_REQUIRE(!last && w->dtype == HMMR_BF16 && U.conv2.scale && U.conv2.shift && !U.shortcut.w &&
-                         ((U.base == 64 && U.depth == 256) || (U.base == 128 && U.depth == 512)),
-                         "resnet: unit %d cannot run as a single-phase tail", u);
+        if (p.end == HMMR_END_CONV3_LAUNCH) {   // 1x1 + bias, + shortcut (no ReLU after the add); k_order 2: the conv3 form of csrc/conv1x1_stream.hip, block 4
+            d = dense_conv(dt, n, T2, Ho, U.base, 1, 1, U.depth, sc_in_c3 ? U.c3sc : U.conv3, out);
+            if (sc_in_c3) { d.in2 = xin; d.cin2 = U.c_in; } else set_residual(d, res, U.depth, H, res_stride);
+            if (pre) { d.out2 = pre; d.scale2 = N.pre_scale; d.shift2 = N.pre_shift; }
+            if (hmmr_conv_gemm(&d, s)) return -2;
+        } else {                              // a fused tail (csrc/bottleneck.hip and the kernels behind it)
             hmmr_tail_desc_t t = {};
-            t.dtype = w->dtype; t.m = n * Ho * Ho; t.c_mid = U.base; t.depth = U.depth;
-            t.h1 = T1; t.hin = H; t.win = H; t.conv2_stride = U.stride; t.ho = Ho; t.wo = Ho;
-            t.w2 = U.conv2.w; t.scale2 = U.conv2.scale; t.shift2 = U.conv2.shift;
+            t.dtype = dt; t.m = n * Ho * Ho; t.c_mid = U.base; t.depth = U.depth; t.ho = t.wo = Ho;
             t.w3 = U.conv3.w; t.scale3 = U.conv3.scale; t.shift3 = U.conv3.shift;
-            t.res = d.res; t.ldr = d.ldr; t.res_strided = d.res_strided; t.res_img_stride = d.res_img_stride;
-            t.res_row_stride = d.res_row_stride; t.res_px_stride = d.res_px_stride;
-            t.out = d.out; t.out_pre = d.out2; t.pre_scale = d.scale2; t.pre_shift = d.shift2;
+            if (p.conv2 == HMMR_CONV2_IN_TAIL) {
+                t.h1 = T1; t.hin = t.win = H; t.w2 = U.conv2.w; t.scale2 = U.conv2.scale; t.shift2 = U.conv2.shift;
+            } else t.h2 = T2;
+            if (p.end == HMMR_END_TAIL_BF16_STRIDE2) {
+                t.conv2_stride = U.stride;
+                set_residual(t, res, U.depth, H, res_stride);
+                t.out = out; t.out_pre = pre;
+                if (pre) { t.pre_scale = N.pre_scale; t.pre_shift = N.pre_shift; }
+            } else {                          // ... with the next unit's preact + conv1 (-> T1, or T2 where this launch still reads T1)
+                if (dt == HMMR_F16X3) {       // fragment-major filters (or one fragment stream); a folded shortcut rides in conv3's K
+                    t.w3 = U.w3_frag;
+                    if (p.conv2 == HMMR_CONV2_IN_TAIL) t.unit_stream = U.unit_stream;
+                    if (p.end == HMMR_END_UNIT_PAIR) t.pair_stream = U.pair_stream;
+                    if (sc_in_c3) { t.scale3 = U.c3sc.scale; t.shift3 = U.c3sc.shift; t.xp = xin; t.c_xp = U.c_in; }
+                }
+                if (p.shortcut == HMMR_SC_IN_TAIL) { t.xp = xin; t.wsc = U.shortcut.w; t.shift_sc = U.shortcut.shift; }
+                else if (!sc_in_c3) set_residual(t, res, U.depth, H, res_stride);
+                t.out = xn; t.pre_scale = N.pre_scale; t.pre_shift = N.pre_shift;
+                t.w1 = dt == HMMR_F16X3 ? U.w1n_frag : N.conv1.w;      // (not read with pair_stream)
+                t.scale1 = N.conv1.scale; t.shift1 = N.conv1.shift; t.relu1 = 1; t.n2 = N.base;
+                t.out_h1 = p.swaps_t1_t2 ? T2 : T1;
+            }
             if (hmmr_bottleneck_tail(&t, s)) return -2;
-        } else if (fuse_tail) {       // conv3 + add + the next unit's preact + conv1 in one launch (csrc/bottleneck.hip)
-            const bool pair = w->dtype == HMMR_F16X3 && U.pair_stream && fuse_tail == 1;        // csrc/unit_pair.hip
-            HMMR_REQUIRE(!last && (w->dtype == HMMR_BF16 || pair || (w->dtype == HMMR_F16X3 && ((U.w3_frag && U.w1n_frag) || U.unit_stream) && fuse_tail <= 2)) &&
-                         U.stride == 1 && write_raw && !write_pre && next_fused &&
-                         next_identity && w->unit[u + 1].base == U.base && w->unit[u + 1].c_in == U.depth &&
-                         ((U.base == 64 && U.depth == 256) || (U.base == 128 && U.depth == 512) || (pair && U.base == 256 && U.depth == 1024)),
-                         "resnet: unit %d cannot fuse its tail", u);
-            const hmmr_resnet_unit_t& N = w->unit[u + 1];
-            hmmr_tail_desc_t t = {};
-            t.dtype = w->dtype; t.m = n * Ho * Ho; t.c_mid = U.base; t.depth = U.depth;
-            if (conv2_in_tail) {      // h2 never exists in HBM; the conv1' output goes to T2 (T1 is still being read
-                                      // by neighbouring tiles' halos), and the two buffers swap roles afterwards
-                HMMR_REQUIRE(U.conv2.scale && U.conv2.shift, "resnet: unit %d cannot fuse its conv2", u);
-                HMMR_REQUIRE((U.conv2.k_order == 2) == (w->dtype == HMMR_F16X3 && U.unit_stream != nullptr),
-                             "resnet: unit %d: a k_order 2 conv2 runs inside the unit only as part of its unit_stream (csrc/b1_unit.hip)", u);
-                t.h1 = T1; t.hin = H; t.win = H; t.w2 = U.conv2.w; t.scale2 = U.conv2.scale; t.shift2 = U.conv2.shift;
-                if (w->dtype == HMMR_F16X3) t.unit_stream = U.unit_stream;
-            } else {
-                t.h2 = T2;
-            }
-            t.w3 = U.conv3.w; t.scale3 = U.conv3.scale; t.shift3 = U.conv3.shift;
-            if (w->dtype == HMMR_F16X3) {            // fragment-major filters (or one fragment stream); a folded shortcut rides in conv3's K
-                t.w3 = U.w3_frag;
-                if (pair) t.pair_stream = U.pair_stream;
-                if (sc_in_c3) { t.scale3 = U.c3sc.scale; t.shift3 = U.c3sc.shift; t.xp = xin; t.c_xp = U.c_in; }
-            }
-            if (sc_in_c3) {
-            } else if (sc_in_tail) {
-                t.xp = xin; t.wsc = U.shortcut.w; t.shift_sc = U.shortcut.shift;
-            } else {
-                t.res = d.res; t.ldr = d.ldr; t.res_strided = d.res_strided; t.res_img_stride = d.res_img_stride;
-                t.res_row_stride = d.res_row_stride; t.res_px_stride = d.res_px_stride;
-            }
-            t.ho = Ho; t.wo = Ho;
-            t.out = xn; t.pre_scale = N.pre_scale; t.pre_shift = N.pre_shift;
-            t.w1 = w->dtype == HMMR_F16X3 ? U.w1n_frag : N.conv1.w;      // (not read with pair_stream)
-            t.scale1 = N.conv1.scale; t.shift1 = N.conv1.shift; t.relu1 = 1; t.n2 = N.base;
-            t.out_h1 = conv2_in_tail ? T2 : T1;
-            if (hmmr_bottleneck_tail(&t, s)) return -2;
-            if (conv2_in_tail) { T* tmp = T1; T1 = T2; T2 = tmp; }
-            h1_ready = true;
-        } else if (hmmr_conv_gemm(&d, s)) return -2;
+            if (p.swaps_t1_t2) { T* tmp = T1; T1 = T2; T2 = tmp; }
+        }
         if (prof_mark(pf)) return -2;
-        have_raw = write_raw;
         cur ^= 1; pcur ^= 1; H = Ho;
     }
-    const T* xraw = X[cur];
     // ---- postnorm BN + ReLU + mean over 7x7
-    {
-        const long long nth = (long long)n * (2048 / 8);
-        hipLaunchKernelGGL(bn_relu_avgpool_kernel<T>, dim3((unsigned)((nth + 255) / 256)), dim3(256), 0, s,
-                           (const T*)xraw, phi, w->post_scale, w->post_shift, n, H * H, 2048);
-        HMMR_CHECK_HIP(hipGetLastError());
-        if (prof_mark(pf)) return -2;
-    }
+    const long long nth = (long long)n * (2048 / 8);
+    hipLaunchKernelGGL(bn_relu_avgpool_kernel<T>, dim3((unsigned)((nth + 255) / 256)), dim3(256), 0, s,
+                       (const T*)X[cur], phi, w->post_scale, w->post_shift, n, H * H, 2048);
+    HMMR_CHECK_HIP(hipGetLastError());
+    if (prof_mark(pf)) return -2;
     return prof_end(pf);
 }
 

@@ -65,6 +65,31 @@ def _dt(d):
     return int(d)
 
 
+def _packer_choices(fold_sc=None, fuse_tail=None, patch_3x3=None, unit_pair=None, b1_stream=None, b1_unit=None, stem_conv1=True,
+                    stream_1x1=None):
+    """HmmrEngine's constructor arguments -> the keyword arguments of packing.pack_resnet.  An argument left at None takes the
+    development switch of devflags.py that names it; the switches without an argument always apply."""
+    def _flag_choice(name):
+        """a switch's value: "0" -> False, "1" -> True, any other word as it stands"""
+        v = devflags.get(name)
+        return {"0": False, "1": True}.get(v, v)
+
+    def pick(arg, flag):
+        return flag if arg is None else arg
+    fsc, fold = _flag_choice("FUSE_SC"), _flag_choice("FOLD_SC")
+    return dict(fuse_preact_blocks=tuple(b for b in devflags.get("FUSE_PREACT").split(",") if b),
+                fuse_tail=pick(fuse_tail, _flag_choice("FUSE_TAIL")),
+                fuse_sc=fsc if isinstance(fsc, bool) else "all",
+                fuse_preact_first=_flag_choice("PREACT_FIRST") is not False,
+                fold_sc=pick(fold_sc, fold if isinstance(fold, bool) else None),          # (None: the packer's default per operand mode)
+                patch_3x3=pick(patch_3x3, int(devflags.get("PATCH_3X3"))),
+                unit_pair=pick(unit_pair, _flag_choice("UNIT_PAIR")),
+                b1_stream=pick(b1_stream, _flag_choice("B1_STREAM") is True),
+                b1_unit=pick(b1_unit, _flag_choice("B1_UNIT") is True),
+                stem_conv1=stem_conv1,
+                stream_1x1=pick(stream_1x1, _flag_choice("STREAM_1X1") is True))
+
+
 class _Workspace(object):
     """Grow-only HBM scratch buffer."""
 
@@ -100,14 +125,6 @@ class HmmrEngine(object):
         self.store = packing.DeviceStore(self.device)
         self.num_conv_layers = num_conv_layers
         self.delta_keys = sorted(int(d) for d in delta_t_values)
-        # packer choices: constructor arguments, defaults overridable by the development switches of devflags.py
-        fuse = tuple(b for b in devflags.get("FUSE_PREACT").split(",") if b)
-        tail = {"0": False, "1": True}.get(devflags.get("FUSE_TAIL"), devflags.get("FUSE_TAIL"))
-        if fuse_tail is not None:
-            tail = fuse_tail
-        fsc = {"0": False, "1": True}.get(devflags.get("FUSE_SC"), "all")
-        pfirst = devflags.get("PREACT_FIRST") != "0"
-        fold = {"0": False, "1": True}.get(devflags.get("FOLD_SC"), None) if fold_sc is None else fold_sc
         # every stage is packed only when its variables exist: a ResNet-only checkpoint (hmr_noS5.ckpt-642561, what
         # FeatureExtractor is given: src/datasets/resnet_extractor.py:31-40) has no AZ_FC_* / single_view_ief* names
         w = weights if weights is not None else {}
@@ -117,16 +134,9 @@ class HmmrEngine(object):
             a_ = np.asarray(v)
             if a_.dtype.kind == "f" and not np.isfinite(a_).all():
                 raise ValueError("variable %r holds %d non-finite value(s)" % (name, int((~np.isfinite(a_)).sum())))
-        self.rw = (packing.pack_resnet(w, self.dtype, self.store, fuse_preact_blocks=fuse, fuse_tail=tail, fuse_sc=fsc,
-                                       fuse_preact_first=pfirst, fold_sc=fold,
-                                       patch_3x3=int(devflags.get("PATCH_3X3")) if patch_3x3 is None else patch_3x3,
-                                       unit_pair=({"0": False, "1": True}.get(devflags.get("UNIT_PAIR"), devflags.get("UNIT_PAIR"))
-                                                  if unit_pair is None else unit_pair),
-                                       b1_stream=(devflags.get("B1_STREAM") == "1") if b1_stream is None else b1_stream,
-                                       b1_unit=(devflags.get("B1_UNIT") == "1") if b1_unit is None else b1_unit,
-                                       stem_conv1=stem_conv1,
-                                       stream_1x1=(devflags.get("STREAM_1X1") == "1") if stream_1x1 is None else stream_1x1)
-                   if "resnet_v2_50/conv1/weights" in w else None)
+        choices = _packer_choices(fold_sc=fold_sc, fuse_tail=fuse_tail, patch_3x3=patch_3x3, unit_pair=unit_pair, b1_stream=b1_stream,
+                                  b1_unit=b1_unit, stem_conv1=stem_conv1, stream_1x1=stream_1x1)
+        self.rw = packing.pack_resnet(w, self.dtype, self.store, **choices) if "resnet_v2_50/conv1/weights" in w else None
         self.tw = (packing.pack_temporal(w, self.temporal_dtype, self.store, num_conv_layers)
                    if assets.temporal_scopes(0)[1] + "/weights" in w else None)
         self.hw = packing.pack_hallucinator(w, self.temporal_dtype, self.store)

@@ -26,14 +26,19 @@ W_TARGET_LOG2 = 14   # filter rows are scaled by a power of two to a maximum in 
 TORCH_DT = {L.HMMR_F32: torch.float32, L.HMMR_BF16: torch.bfloat16, L.HMMR_F16X3: SPLIT}
 
 
+def _hi_lo(t):
+    """fp32 tensor -> its two fp16 halves (hi, lo): hi = fp16(t), lo = fp16(t - hi)."""
+    hi = t.to(SPLIT_HALF)
+    return hi, (t - hi.to(torch.float32)).to(SPLIT_HALF)
+
+
 def to_split(t):
     """fp32 tensor [..., C] (C % 8 == 0) -> int32 tensor [..., C] in the split (f16x3) layout: every group of 8
     channels is 32 bytes, [hi x8][lo x8] with hi = fp16(x), lo = fp16(x - hi), x clamped to +-65504 (include/hmmr_hip.h)."""
     t = t.to(torch.float32).clamp(-SPLIT_MAX, SPLIT_MAX)
     C = t.shape[-1]
     assert C % 8 == 0, "split tensors need a channel count that is a multiple of 8"
-    hi = t.to(SPLIT_HALF)
-    lo = (t - hi.to(torch.float32)).to(SPLIT_HALF)
+    hi, lo = _hi_lo(t)
     g = torch.stack([hi.reshape(t.shape[:-1] + (C // 8, 8)), lo.reshape(t.shape[:-1] + (C // 8, 8))], dim=-2)
     return g.reshape(t.shape[:-1] + (2 * C,)).contiguous().view(torch.int32)
 
@@ -103,21 +108,32 @@ def scale_rows(w_rows, k):
     return (np.asarray(w_rows, np.float64) * np.exp2(k.astype(np.float64))[:, None]).astype(np.float32)
 
 
-def pack_frag_major(w_nk):
-    """[n_out][K] fp32 -> fp16 [n_out / 32][K / 16][64 lanes][2 (hi, lo)][8]: the MFMA A-operand fragments of a split
-    filter bank, one coalesced 2 KB read per (32-row block, 16-wide K chunk); lane = 32 * (k half) + row
-    (hmmr_tail_desc_t, csrc/bottleneck_split.hip).  Rows carry the power-of-two scale of row_pow2()."""
+def _split_scale(scale, k, n):
+    """The epilogue scale [n] of a split filter bank whose rows carry 2^k (row_pow2): scale * 2^-k, exact (a power of two times a
+    float32); scale None (a bias-only layer), or shorter than n (padding rows): ones there, i.e. pure powers of two."""
+    sc = np.ones(n, np.float64)
+    if scale is not None:
+        sc[:len(scale)] = np.asarray(scale, np.float64)
+    return (sc * np.exp2(-np.asarray(k, np.float64))).astype(np.float32)
+
+
+def _frag_planes(w_nk, plane_axis):
+    """[n][K] fp32 -> fp16 [n / 32][K / 16][64 lanes][8] with the (hi, lo) plane as axis `plane_axis`: the MFMA A-operand fragments
+    of a split filter bank whose rows carry the power-of-two scale of row_pow2().  A fragment = 32 rows x 16 K:
+    lane = 32 * (k half) + row, 8 halves = W[32 rb + row][16 kc + 8 half .. + 7]."""
     w_nk = np.ascontiguousarray(w_nk, dtype=np.float32)
     t = torch.from_numpy(scale_rows(w_nk, row_pow2(w_nk)))
     n, K = t.shape
     assert n % 32 == 0 and K % 16 == 0, (n, K)
-    hi = t.to(SPLIT_HALF)
-    lo = (t - hi.to(torch.float32)).to(SPLIT_HALF)
+    # rb, row, kc, half, e -> rb, kc, half * 32 + row, e
+    planes = [x.reshape(n // 32, 32, K // 16, 2, 8).permute(0, 2, 3, 1, 4).reshape(n // 32, K // 16, 64, 8) for x in _hi_lo(t)]
+    return torch.stack(planes, dim=plane_axis)
 
-    def frag(x):
-        x = x.reshape(n // 32, 32, K // 16, 2, 8)                # rb, row, kc, half, e
-        return x.permute(0, 2, 3, 1, 4).reshape(n // 32, K // 16, 64, 8)
-    return torch.stack([frag(hi), frag(lo)], dim=3).contiguous()   # [rb, kc, lane, 2, 8]
+
+def pack_frag_major(w_nk):
+    """[n_out][K] fp32 -> fp16 [n_out / 32][K / 16][64 lanes][2 (hi, lo)][8]: the fragments of _frag_planes, one coalesced 2 KB
+    read per (32-row block, 16-wide K chunk) (hmmr_tail_desc_t, csrc/bottleneck_split.hip)."""
+    return _frag_planes(w_nk, 3).contiguous()
 
 
 def pack_conv3x3_stream(w_hwio, k=None, bf16=False):
@@ -141,13 +157,10 @@ def pack_conv3x3_stream(w_hwio, k=None, bf16=False):
     if k is None:
         k = row_pow2(w.reshape(T * cin, cout).T)
     t = torch.from_numpy((w * np.exp2(np.asarray(k, np.float64))).astype(np.float32))
-    hi = t.to(SPLIT_HALF)
-    lo = (t - hi.to(torch.float32)).to(SPLIT_HALF)
-
-    def frag(x):
-        x = x.reshape(T, cin // 16, 2, 8, cout // tw, tw // 32, 32)      # tap, c16, half, e, tile, rb, row
-        return x.permute(4, 1, 0, 5, 2, 6, 3).reshape(cout // tw, T * (cin // 16), tw // 32, 64, 8)
-    return torch.stack([frag(hi), frag(lo)], dim=3).contiguous()          # [tile, kt, rb, plane, lane, 8]
+    # tap, c16, half, e, tile, rb, row -> tile, kt, rb, lane, e
+    planes = [x.reshape(T, cin // 16, 2, 8, cout // tw, tw // 32, 32).permute(4, 1, 0, 5, 2, 6, 3)
+               .reshape(cout // tw, T * (cin // 16), tw // 32, 64, 8) for x in _hi_lo(t)]
+    return torch.stack(planes, dim=3).contiguous()                        # [tile, kt, rb, plane, lane, 8]
 
 
 def pack_conv1x1_stream(w_hwio, k=None):
@@ -176,19 +189,7 @@ def pack_pair_stream(w3_nk, w1_nk):
     depth, K3 = w3_nk.shape
     n2 = w1_nk.shape[0]
     assert w1_nk.shape[1] == depth and depth % 32 == 0 and K3 % 16 == 0 and n2 % 32 == 0, (w3_nk.shape, w1_nk.shape)
-
-    def planar(w_nk):
-        t = torch.from_numpy(scale_rows(w_nk, row_pow2(w_nk)))
-        n, K = t.shape
-        hi = t.to(SPLIT_HALF)
-        lo = (t - hi.to(torch.float32)).to(SPLIT_HALF)
-
-        def frag(x):
-            x = x.reshape(n // 32, 32, K // 16, 2, 8)                # rb, row, kc, half, e
-            return x.permute(0, 2, 3, 1, 4).reshape(n // 32, K // 16, 64, 8)
-        return torch.stack([frag(hi), frag(lo)], dim=2)              # [rb, kc, plane, lane, 8]
-
-    f3, f1 = planar(w3_nk), planar(w1_nk)
+    f3, f1 = _frag_planes(w3_nk, 2), _frag_planes(w1_nk, 2)          # [rb, kc, plane, lane, 8]
     nch, na, nf2 = depth // 32, K3 // 16, n2 // 32
     nb = 2 * nf2
     ft = na + nb
@@ -218,19 +219,7 @@ def pack_b1_unit_stream(w2_hwio, k2, w3_nk, w1_nk):
     depth, K3 = w3_nk.shape
     assert depth == 256 and K3 in (64, 128) and w1_nk.shape == (64, 256), (w3_nk.shape, w1_nk.shape)
     parts = [pack_conv3x3_stream(w2, k2).reshape(-1, 2, 64, 8)]          # [36 x 2 fragments][plane][lane][8]
-
-    def planar(w_nk):
-        t = torch.from_numpy(scale_rows(w_nk, row_pow2(w_nk)))
-        n, K = t.shape
-        hi = t.to(SPLIT_HALF)
-        lo = (t - hi.to(torch.float32)).to(SPLIT_HALF)
-
-        def frag(x):
-            x = x.reshape(n // 32, 32, K // 16, 2, 8)                # rb, row, kc, half, e
-            return x.permute(0, 2, 3, 1, 4).reshape(n // 32, K // 16, 64, 8)
-        return torch.stack([frag(hi), frag(lo)], dim=2)              # [rb, kc, plane, lane, 8]
-
-    f3, f1 = planar(w3_nk), planar(w1_nk)
+    f3, f1 = _frag_planes(w3_nk, 2), _frag_planes(w1_nk, 2)          # [rb, kc, plane, lane, 8]
     nch = depth // 32
     parts.append(f3[0])                                              # A(0): conv3 row block 0, K3 / 16 fragments
     for c in range(nch):
@@ -312,11 +301,7 @@ def _layer(store, w_packed, dtype, scale=None, shift=None):
         w_packed = np.asarray(w_packed, np.float32)
         k = row_pow2(w_packed)
         w_packed = scale_rows(w_packed, k)
-        inv = np.exp2(-k.astype(np.float64))
-        sc = np.ones(len(k), np.float64)
-        if scale is not None:
-            sc[:len(scale)] = np.asarray(scale, np.float64)
-        scale = (sc * inv).astype(np.float32)          # exact: a power of two times a float32
+        scale = _split_scale(scale, k, len(k))
     lay.w = store.put(w_packed, TORCH_DT[dtype]).data_ptr()
     lay.scale = store.vec(scale).data_ptr() if scale is not None else None
     lay.shift = store.vec(shift).data_ptr() if shift is not None else None
@@ -330,10 +315,9 @@ def _layer_stream3x3(store, w_hwio, scale, shift, bf16=False):
         lay.w = store.put_tensor(pack_conv3x3_stream(w_hwio, bf16=True)).data_ptr()
         lay.scale = store.vec(scale).data_ptr()
     else:
-        rows = pack_conv_weight(w_hwio)[:w_hwio.shape[3]]
-        k = row_pow2(rows)
+        k = row_pow2(pack_conv_weight(w_hwio)[:w_hwio.shape[3]])
         lay.w = store.put_tensor(pack_conv3x3_stream(w_hwio, k)).data_ptr()
-        lay.scale = store.vec((np.asarray(scale, np.float64) * np.exp2(-k.astype(np.float64))).astype(np.float32)).data_ptr()
+        lay.scale = store.vec(_split_scale(scale, k, len(k))).data_ptr()
     lay.shift = store.vec(shift).data_ptr()
     lay.k_order = 2
     return lay
@@ -346,8 +330,7 @@ def _layer_stream1x1(store, w_hwio, scale, shift):
     cout = w_hwio.shape[3]
     k = row_pow2(pack_conv_weight(w_hwio)[:cout])
     lay.w = store.put_tensor(pack_conv1x1_stream(w_hwio, k)).data_ptr()
-    sc = np.ones(cout, np.float64) if scale is None else np.asarray(scale, np.float64)
-    lay.scale = store.vec((sc * np.exp2(-k.astype(np.float64))).astype(np.float32)).data_ptr()
+    lay.scale = store.vec(_split_scale(scale, k, cout)).data_ptr()
     lay.shift = store.vec(shift).data_ptr()
     lay.k_order = 2
     return lay
@@ -442,9 +425,8 @@ def _pack_resnet_py(w, dtype, store, fuse_preact_blocks=("block1", "block2", "bl
             # row scaling as the layer above, so the layer's scale / shift apply)
             u.conv1_frag = store.put_tensor(pack_frag_major(np.asarray(w[scope + "/conv1/weights"], np.float32)[0, 0].T)).data_ptr()
         s, b = fold_bn(w, scope + "/conv2/BatchNorm")
-        # (bf16, round 4: blocks 3-4 only -- the conv2 of blocks 1-2 runs inside the fused bf16 units, which read the tap-major order)
         stream = dtype in (L.HMMR_F16X3, L.HMMR_BF16) and patch_3x3 == 2 and patch_3x3 is not True
-        # (bf16: the conv2 of blocks 1-2 runs inside the fused bf16 units, which read the tap-major order -- unless fuse_tail="conv2b1"
+        # (bf16, round 4: blocks 3-4 only -- the conv2 of blocks 1-2 runs inside the fused bf16 units, which read the tap-major order -- unless fuse_tail="conv2b1"
         #  keeps block 2's outside, as launches of the stream kernel)
         b16_min = 128 if (stream and fuse_tail == "conv2b1") else 256
         kord = int(bool(patch_3x3) and stride == 1 and ((dtype == L.HMMR_F16X3 and (base >= 128 or (stream and (b1_stream or b1_unit)))) or
@@ -700,10 +682,8 @@ def pack_smpl(smpl, store, joint_type="cocoplus", split=True, impl=None):
     # (an entry beyond 65504 / 2^13 = 7.99 m would become inf in torch's fp16 cast: no such body model, but then the vector form it is)
     if split and float(np.abs(dirs).max()) * 8192.0 < 65504.0:
         ds = torch.from_numpy(dirs.astype(np.float64) * 8192.0).to(torch.float32)            # exact: a power of two
-        hi = ds.to(SPLIT_HALF)
-        lo = (ds - hi.to(torch.float32)).to(SPLIT_HALF)
-        frag = lambda x: x.reshape(14, 2, 8, 3, vpad).permute(0, 3, 1, 4, 2)                # kc, c, h, v, e
-        sc.dirs_split = store.put_tensor(torch.stack([frag(hi), frag(lo)], dim=2).contiguous()).data_ptr()      # kc, c, plane, h, v, e
+        planes = [x.reshape(14, 2, 8, 3, vpad).permute(0, 3, 1, 4, 2) for x in _hi_lo(ds)]  # kc, c, h, v, e
+        sc.dirs_split = store.put_tensor(torch.stack(planes, dim=2).contiguous()).data_ptr()     # kc, c, plane, h, v, e
     sc.j_template = store.put(j_template.astype(np.float32)).data_ptr()
     sc.j_shapedirs = store.put(j_shapedirs.astype(np.float32)).data_ptr()
     sc.parents = store.put(np.asarray(smpl["parents"]).astype(np.int32), torch.int32).data_ptr()

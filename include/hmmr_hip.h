@@ -248,7 +248,8 @@ typedef struct {
     int c_in, base, depth, stride;
     int fuse_preact;           /* 1: conv1/shortcut apply the preact while staging their operand;
                                   0: the previous unit's conv3 writes the preact tensor */
-    int fuse_tail;             /* 4: stride-2 unit: conv2 + conv3 + add as one launch, no next conv1;
+    int fuse_tail;             /* what the unit ends in (hmmr_unit_plan_t.end, HMMR_END_*: the dtype and the streams above pick the kernel; 0: HMMR_END_CONV3_LAUNCH)
+                                  4: stride-2 unit: conv2 + conv3 + add as one launch, no next conv1;
                                   3: as 2, and the unit's conv shortcut is computed in that launch too (c_in 64);
                                   2: as 1, with this unit's conv2 inside the same launch as well;
                                   1: this unit's conv3 + add and the NEXT unit's preact + conv1 run as one
@@ -354,6 +355,36 @@ size_t hmmr_resnet50_workspace_bytes(int n, int dtype);
  * phi has n + n_zero rows, the workspace must be sized for n + n_zero. */
 int hmmr_resnet50_fwd(const hmmr_resnet_weights_t* w, const float* images, int n, int n_zero,
                       float* phi, void* ws, size_t ws_bytes, void* stream, float* prof_ms);
+
+/* What hmmr_resnet50_fwd launches for one unit: decided for all 16 units, from the unit table, the frame count and hmmr_debug_t,
+ * BEFORE the first launch (an inconsistent table is refused with the unit named and nothing queued), then issued in order.
+ * Profile slots per unit: [shortcut, when it is not HMMR_SC_NONE] conv1 conv2 conv3 -- a layer without a launch of its own
+ * keeps its (empty) slot. */
+enum { HMMR_SC_NONE = 0,             /* identity / subsampled shortcut: no filter bank */
+       HMMR_SC_LAUNCH,               /* a 1x1 GEMM of its own */
+       HMMR_SC_LAUNCH_WITH_CONV1,    /* ... with conv1 as extra output columns (sc_c1) */
+       HMMR_SC_IN_CONV3,             /* folded into conv3's K (c3sc), wherever conv3 runs */
+       HMMR_SC_IN_TAIL };            /* computed inside the fused tail (fuse_tail 3) */
+enum { HMMR_CONV1_LAUNCH = 0,
+       HMMR_CONV1_READY };           /* no launch: the stem, the previous unit's tail or this unit's shortcut launch wrote it */
+enum { HMMR_CONV2_LAUNCH = 0, HMMR_CONV2_IN_TAIL };
+enum { HMMR_END_CONV3_LAUNCH = 0,    /* conv3 + add as one GEMM (fuse_tail 0, or a demoted unit pair) */
+       HMMR_END_TAIL_BF16,           /* csrc/bottleneck.hip: conv3 + add + the next unit's preact + conv1 (fuse_tail 1 .. 3) */
+       HMMR_END_TAIL_BF16_STRIDE2,   /* csrc/bottleneck.hip, single phase: conv2 + conv3 + add, no next conv1 (fuse_tail 4) */
+       HMMR_END_TAIL_SPLIT,          /* csrc/bottleneck_split.hip: the LDS-panel tail (w3_frag / w1n_frag) */
+       HMMR_END_B1_UNIT,             /* csrc/b1_unit.hip: conv2 .. the next conv1 of a block-1 unit (unit_stream) */
+       HMMR_END_UNIT_PAIR };         /* csrc/unit_pair.hip (pair_stream) */
+typedef struct {
+    int shortcut, conv1, conv2, end; /* HMMR_SC_* / HMMR_CONV1_* / HMMR_CONV2_* / HMMR_END_* */
+    int reads_fused_preact;          /* conv1 / the shortcut read the raw trunk and pre-activate while staging */
+    int writes_raw, writes_pre;      /* the end writes the raw trunk / the next unit's pre-activated tensor */
+    int pair_demoted;                /* fewer pixels than hmmr_debug_t.pair_min_pixels: the two launches instead of the unit pair */
+    int swaps_t1_t2;                 /* the tail wrote the next conv1 into the OTHER bottleneck buffer (conv2 ran inside it) */
+    int leaves_h1;                   /* the next unit's conv1 is HMMR_CONV1_READY */
+} hmmr_unit_plan_t;
+/* Host only: no HIP call, reads the same hmmr_debug_t as the pass.  n_total = n + n_zero.  -1: the table is inconsistent
+ * (hmmr_last_error names the unit). */
+int hmmr_resnet50_plan(const hmmr_resnet_weights_t* w, int n_total, hmmr_unit_plan_t out[HMMR_RESNET_UNITS]);
 
 /* ------------------------------------------------------------------------- *
  * f_movie temporal encoder: az_fc2_groupnorm / az_fc_block2
