@@ -172,6 +172,26 @@ class RenderDesc(C.Structure):
                 ("rgb", _vp), ("alpha", _fp), ("face_index", _ip), ("ws", _vp), ("ws_bytes", C.c_size_t)]
 
 
+SCENE_MAX_TRACKS = 16
+
+
+class SceneTrack(C.Structure):
+    """hmmr_scene_track_t: one person track of the scene view (csrc/render.hip)"""
+    _fields_ = [("verts", _fp), ("ld_verts", C.c_int64), ("cams", _fp), ("ld_cam", C.c_int64), ("geom", _fp),
+                ("priority", _fp), ("start", C.c_int), ("end", C.c_int), ("color", C.c_float * 3)]
+
+
+class SceneDesc(C.Structure):
+    """hmmr_scene_desc_t: one call of the scene view (csrc/render.hip)"""
+    _fields_ = [("tracks", C.POINTER(SceneTrack)), ("n_tracks", C.c_int), ("faces", _ip),
+                ("nv", C.c_int), ("nf", C.c_int), ("n_frames", C.c_int), ("size", C.c_int),
+                ("out_h", C.c_int), ("out_w", C.c_int), ("bg_color", C.c_float * 3),
+                ("light_dir", C.c_float * 3), ("light_int_ambient", C.c_float), ("light_int_directional", C.c_float),
+                ("light_color_ambient", C.c_float * 3), ("light_color_directional", C.c_float * 3),
+                ("bg_mode", C.c_int), ("bg_image", _vp), ("frame_h", C.c_int), ("frame_w", C.c_int),
+                ("rgb", _vp), ("alpha", _fp), ("face_index", _ip), ("owner", _ip), ("ws", _vp), ("ws_bytes", C.c_size_t)]
+
+
 SKELETON_MAX_RADIUS, COLLAGE_MAX_PANEL_WIDTH = 1024, 4096
 
 
@@ -240,6 +260,8 @@ SIGNATURES = {
                                       _fp, _fp, _fp, _vp]),
     "hmmr_render_workspace_bytes": (C.c_size_t, [C.c_int, C.c_int, C.c_int]),
     "hmmr_render_mesh": (C.c_int, [C.POINTER(RenderDesc), _vp]),
+    "hmmr_render_scene_workspace_bytes": (C.c_size_t, [C.c_int, C.c_int, C.c_int, C.c_int]),
+    "hmmr_render_scene": (C.c_int, [C.POINTER(SceneDesc), _vp]),
     "hmmr_skeleton_radius": (C.c_int, [C.c_int, C.c_int]),
     "hmmr_draw_skeleton": (C.c_int, [C.POINTER(SkeletonDesc), _vp]),
     "hmmr_collage_width": (C.c_int, [C.c_int, C.c_int, C.c_int]),

@@ -18,6 +18,11 @@ chunks on the device (util/render/video.render_views), written as PNGs with PIL 
 into the two mp4s by the reference's command line.  The skeleton's draw list is the reference's; the pixels of its
 primitives follow the integer rules of include/hmmr_hip.h, whose agreement with OpenCV at primitive boundaries has not been
 measured; no text is drawn.
+
+    render_tracks(output_path, tracks, frames, faces=...)
+
+is not the reference's (it renders one track per video): all tracks of a video over each original frame, one PNG per frame
+and one mp4 (util/render/video.render_scene, include/hmmr_hip.h: hmmr_render_scene).
 """
 from __future__ import annotations
 
@@ -216,4 +221,76 @@ def render_preds(output_path, config, preds, images, images_orig, trim_length, i
         result["videos"] = (vid_path, vid_path_crop)
     else:
         result["note"] = "ffmpeg failed: the PNG frames are left in %s and %s" % (output_path, output_crop)
+    return result
+
+
+def _clip_tracks(tracks, a, b, colors, priority):
+    """The tracks present in frames [a, b), their rows and ranges cut to it: (tracks, colors, priority) for video.render_scene
+    on frames[a:b].  Each keeps the colour of its index in the whole video."""
+    from ..util.render.raster import scene_color
+    part, cols, prio = [], [], []
+    for t, (records, layout, (start, end), params) in enumerate(tracks):
+        s, e = max(start, a), min(end, b)
+        if s >= e:
+            continue
+        rows = slice(s - start, e - start)
+        rec = {k: records[k][rows] for k in ('cams', 'verts')} if isinstance(records, dict) else records[rows]
+        part.append((rec, layout, (s - a, e - a), params[rows]))
+        cols.append(scene_color(t, colors))
+        prio.append(priority[t][rows] if priority is not None and priority[t] is not None else None)
+    return part, cols, prio
+
+
+def render_tracks(output_path, tracks, frames, faces=None, face_path='src/tf_smpl/smpl_faces.npy', trim_length=0, chunk=64,
+                  max_img_size=720, colors=None, priority=None, device=None):
+    """Renders frames [trim_length, F - trim_length) of a video with ALL its tracks in each frame:
+
+        output_path/frame%06d.png   every person present in the frame over the original frame (at most 720 pixels)
+
+    tracks: per track (records_or_dict, layout, (start, end), image_og_params), as util/render/video.render_scene takes
+    them; frames: uint8 [F,H,W,3], host or device.  The frames are rendered `chunk` at a time, each track cut to the
+    chunk, and come to the host as finished uint8 frames.  colors / priority: as video.render_scene, per track of the
+    whole video.  A chunk in which nobody is tracked shows the resized frames.
+    Returns None if output_path + '.mp4' exists already ("Video already exists!"), else a dict: the folder, the number of
+    frames written, and `video`: the mp4 path, or None with `note` saying that no ffmpeg was found (or that it failed)
+    and the PNG frames were left in place."""
+    from PIL import Image
+    from ..util.render import video
+    from ..util.render.nmr_renderer import load_faces
+    from ..util.render.raster import MeshFaces
+    vid_path = output_path + '.mp4'
+    if os.path.exists(vid_path):
+        print('Video already exists!')
+        return None
+    if not os.path.exists(output_path):
+        os.mkdir(output_path)
+    mesh_faces = faces if isinstance(faces, MeshFaces) else MeshFaces(faces if faces is not None else load_faces(face_path))
+    if device is None:
+        r0 = tracks[0][0]
+        device = r0.device if torch.is_tensor(r0) else torch.device("cuda", torch.cuda.current_device())
+    lo, hi = trim_length, len(frames) - trim_length
+    written = 0
+    for a in range(lo, hi, chunk):
+        b = min(a + chunk, hi)
+        part, cols, prio = _clip_tracks(tracks, a, b, colors, priority)
+        if not part:
+            # nobody here: one row of non-finite vertices draws nothing (include/hmmr_hip.h), so alpha is 0 everywhere
+            nv = mesh_faces.max_index + 1
+            part = [({"cams": torch.ones((1, 3), device=device), "verts": torch.full((1, nv, 3), float("nan"), device=device)},
+                     None, (0, 1), [{"start_pt": [0, 0], "scale": 1.0, "im_shape": [IMG_SIZE, IMG_SIZE]}])]
+            cols, prio = ['blue'], [None]
+        out = video.render_scene(part, frames[a:b], mesh_faces, max_img_size=max_img_size, colors=cols, priority=prio,
+                                 device=device).cpu().numpy()
+        for j in range(a, b):
+            Image.fromarray(out[j - a]).save(os.path.join(output_path, 'frame{:06d}.png'.format(j - trim_length)))
+            written += 1
+    print('Converting them to video..')
+    made = make_video(vid_path, output_path)
+    result = {"frames": output_path, "n_frames": written, "video": None, "note": None}
+    if made is None:
+        result["note"] = "no ffmpeg on PATH: the PNG frames are left in %s" % output_path
+    elif made:
+        result["video"] = vid_path
+    else:
+        result["note"] = "ffmpeg failed: the PNG frames are left in %s" % output_path
     return result

@@ -14,6 +14,9 @@ render_preds' second folder, the 'orig' panel).  PNG and mp4 writing is evaluati
 (cv2.putText) is not provided.  The skeleton's draw list is the reference's, executed; the pixels of its discs, rings and
 lines follow the integer rules of include/hmmr_hip.h, and their agreement with OpenCV's scan conversion at primitive
 boundaries has not been measured.
+
+`render_scene` is not the reference's: it draws ALL tracks of a video into each original frame in one hmmr_render_scene call
+(the reference renders one track per video), layering the persons of a frame by camera scale; see include/hmmr_hip.h.
 """
 from __future__ import annotations
 
@@ -23,6 +26,7 @@ import torch
 from ... import _lib as L
 from .collage import compose_collage, skeleton_panels
 from .handoff import orig_image_geometry
+from . import raster
 from .raster import COLORS, MeshFaces, render_mesh, rodrigues
 
 
@@ -100,3 +104,35 @@ def render_views(records, layout, frames_uint8, image_og_params, faces, crops=No
     if 'collage' in views:
         out['collage'] = compose_collage(out['crop'], out['skel'], out['orig'], out['rotated'])
     return out
+
+
+def render_scene(tracks, frames_uint8, faces, max_img_size=720, colors=None, priority=None, device=None):
+    """Every tracked person over the original frames, one raster per frame (hmmr_render_scene; the layering rule is this
+    project's, the reference has no multi-person view).
+
+    tracks: a list of (records_or_dict, layout, (start, end), image_og_params) per track: what predict_videos /
+    predict_records (packed records + layout) or predict_all_images (a dict, layout None) return for the track, its frame
+    range in frames_uint8 [F,H,W,3] and the end - start dicts of process_tracks / process_image.  Row f - start of a
+    track is the person in frame f; cams / verts are read in place.  The geom rows come from orig_image_geometry, as in
+    render_views.  A frame's persons are layered by `priority[t]` ([end - start] keys, larger in front) where given, else
+    by the scale of the camera in the original image, larger in front; ties go to the lower track.
+    colors: per track a raster.COLORS name or an rgb triple; the default cycles through raster.SCENE_COLORS ('blue',
+    'pink', 'mint', 'orange', 'yellow', 'green', 'red', 'mint2', 'green2') by track index.
+    -> uint8 [F, h', w', 3] on the device, (h', w') = orig_output_size(frame, max_img_size)[:2]."""
+    if device is None:
+        r0 = tracks[0][0]
+        device = r0.device if torch.is_tensor(r0) else torch.device("cuda", torch.cuda.current_device())
+    faces = faces if isinstance(faces, MeshFaces) else MeshFaces(faces)
+    hw = tuple(frames_uint8.shape[1:3])
+    h, w, S = orig_output_size(hw, max_img_size)
+    fr = frames_uint8 if torch.is_tensor(frames_uint8) else torch.from_numpy(np.ascontiguousarray(frames_uint8))
+    scene = []
+    for t, (records, layout, (start, end), params) in enumerate(tracks):
+        cams, verts = _cams_verts(records, layout, device)
+        if len(params) != end - start:
+            raise ValueError("track %d: %d image_og_params for the range (%d, %d)" % (t, len(params), start, end))
+        geom = np.stack([orig_image_geometry(params[i], hw, max_img_size) for i in range(end - start)])
+        scene.append({"verts": verts, "cams": cams, "range": (start, end), "geom": geom,
+                      "priority": priority[t] if priority is not None else None})
+    return raster.render_scene(scene, faces, S, fr.shape[0], colors=colors, bg_mode=L.RENDER_BG_FRAME, bg_image=fr.to(device),
+                               out_hw=(h, w))["rgb"]

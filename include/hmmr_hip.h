@@ -665,6 +665,62 @@ size_t hmmr_render_workspace_bytes(int n, int nv, int nf);
 int hmmr_render_mesh(const hmmr_render_desc_t* d, void* stream);
 
 /* ------------------------------------------------------------------------- *
+ * Scene view (csrc/render.hip; additive to ABI 19): every tracked person of a video in one frame.  The reference has no
+ * multi-person view (demo_video.py and run_video.py draw one track per video); the layering rule below is this project's.
+ *   tracks       t = 0 .. n_tracks-1 share one topology (nv, nf, faces).  Track t covers frames [start_t, end_t) inside
+ *                [0, n_frames); instance (t, f) exists iff start_t <= f < end_t and uses row f - start_t of the track's
+ *                verts / cams / geom / priority, which are read in place (row strides, as hmmr_render_handoff).
+ *   per instance camera change, projection, face planes, z', depth range, shading and tie rules are hmmr_render_mesh's
+ *                (the same device code), with the track's colour and no rotation.
+ *   order        the instances of a frame are visited by a key, descending; ties go to the lower track index; a
+ *                non-finite key sorts last.  The key is priority[f - start_t] where the track gives one, else the fp32
+ *                scale of the camera the projection uses (new_cam[0] after the geom change, cam[0] without geom): under
+ *                the weak-perspective camera a larger projected person is the nearer one.
+ *   subpixel     its owner is the FIRST instance in that order with any face covering it at depth in [0.1, 100]; its face
+ *                is that instance's nearest face (ties: lower face index); its colour that face's shading in the owner's
+ *                colour.  A later person never shows through an earlier one, whatever their z: the z of two people's
+ *                SMPL frames is not comparable.
+ *   pixel        2x2 mean with the background colour for uncovered subpixels, alpha = covered / 4, composited once as
+ *                hmmr_render_mesh does, in the modes HMMR_RENDER_BG_COLOR and HMMR_RENDER_BG_FRAME.  A frame without an
+ *                instance has alpha 0 everywhere and shows the resized frame (or the background colour).
+ * With n_tracks = 1 the result equals hmmr_render_mesh on that track bit for bit in rgb, alpha and face_index.
+ * The frames go in slabs of max(1, 64 / n_tracks) frames, so at most 64 instances are in the workspace at a time and
+ * it does not grow with n_frames; the order is fixed and nothing passes between workgroups, so a frame renders the
+ * same bits alone, in a batch, or beside other streams.
+ * ------------------------------------------------------------------------- */
+#define HMMR_SCENE_MAX_TRACKS 16
+typedef struct {
+    const float* verts; int64_t ld_verts;     /* [end - start] rows of >= 3 nv floats */
+    const float* cams; int64_t ld_cam;        /* [end - start] rows of >= 3 floats: s, tx, ty */
+    const float* geom;                        /* NULL, or [end - start][5] as hmmr_render_desc_t.geom */
+    const float* priority;                    /* NULL (order by camera scale), or [end - start] fp32 keys on the device */
+    int start, end;                           /* 0 <= start < end <= n_frames */
+    float color[3];
+} hmmr_scene_track_t;
+typedef struct {
+    const hmmr_scene_track_t* tracks;         /* HOST array of n_tracks entries; it travels to the kernels by value */
+    int n_tracks;                             /* 1 .. HMMR_SCENE_MAX_TRACKS */
+    const int32_t* faces;                     /* [nf][3], indices in [0, nv): the caller's precondition */
+    int nv, nf, n_frames, size;               /* limits as hmmr_render_mesh's (n_frames as its n) */
+    int out_h, out_w;                         /* <= size */
+    float bg_color[3];
+    float light_dir[3];                       /* used as given (not normalised) */
+    float light_int_ambient, light_int_directional;
+    float light_color_ambient[3], light_color_directional[3];
+    int bg_mode;                              /* HMMR_RENDER_BG_COLOR or HMMR_RENDER_BG_FRAME */
+    const void* bg_image;                     /* HMMR_RENDER_BG_FRAME: uint8 [n_frames][frame_h][frame_w][3] */
+    int frame_h, frame_w;
+    unsigned char* rgb;                       /* [n_frames][out_h][out_w][3] */
+    float* alpha;                             /* NULL or [n_frames][out_h][out_w] */
+    int32_t* face_index;                      /* NULL or [n_frames][2S][2S]: the owner's covering face, -1 where uncovered */
+    int32_t* owner;                           /* NULL or [n_frames][2S][2S]: the owning track's index, -1 where uncovered */
+    void* ws; size_t ws_bytes;                /* hmmr_render_scene_workspace_bytes(...) bytes, device memory */
+} hmmr_scene_desc_t;
+/* Device workspace for a call (0: bad arguments): that of one slab, the same for every n_frames >= max(1, 64 / n_tracks). */
+size_t hmmr_render_scene_workspace_bytes(int n_frames, int n_tracks, int nv, int nf);
+int hmmr_render_scene(const hmmr_scene_desc_t* d, void* stream);
+
+/* ------------------------------------------------------------------------- *
  * The skeleton panel and the 2x2 collage of the demo (csrc/collage.hip; additive to ABI 19).
  *
  * hmmr_draw_skeleton replaces draw_skeleton (src/util/render/render_utils.py:38-234) as visualize_img calls it
