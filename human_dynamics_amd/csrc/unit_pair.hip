@@ -27,7 +27,8 @@
 //   * software pipeline over chunks: iteration `it` issues the MFMAs of conv3 chunk it and of conv1' K step it-2
 //     ALTERNATELY (the dependent accumulator chains of either never run back to back) while the vector unit does the
 //     epilogue of chunk it-1.  Rounding points, product order (x.lo*w.hi, x.hi*w.lo, x.hi*w.hi) and K order are those of
-//     gemm_conv.hip: the results are bit-identical to the two launches (tested through the whole ResNet).
+//     gemm_conv.hip: the results are bit-identical to the two launches (tested through the whole ResNet
+//     and alone: tests/test_gpu_unit_pair.py).
 // Round 5: PERSISTENT WORKGROUPS for the block-2 shapes once a launch is at least two rounds of workgroups (one workgroup per CU, tiles
 // b, b + grid, b + 2 grid ...: a.tpw of them): the ring is left streaming across the tile boundary (the stream is periodic and the loop already requests NS - 1 slabs past
 // the end), the constants stay in LDS, so the second tile's prologue is its panel + first shortcut chunk instead of 96 KB of ring + both

@@ -807,3 +807,125 @@ def b1_unit(h1, conv2, w3_hwio, bias3, pre, w1_hwio, bn1, res=None, shortcut=Non
     L.check(lib.hmmr_bottleneck_tail(C.byref(d), torch.cuda.current_stream(dev).cuda_stream), "hmmr_bottleneck_tail")
     torch.cuda.synchronize(dev)
     return out, h1n
+
+
+PAIR_NAN_WORD = 0x7e007e00          # two fp16 NaNs: what the guard rows / columns of a UnitPairCall's inputs hold
+PAIR_SENTINEL = 0x5a5a5a5a          # ... and what its outputs hold before the launch, valid rows included
+
+
+class UnitPairCall(object):
+    """Test/utility entry for the register-resident unit pair (hmmr_tail_desc_t.pair_stream, csrc/unit_pair.hip; f16x3) ALONE, and for
+    the two hmmr_conv_gemm launches it replaces (conv3 + shortcut -> trunk; fused-preact conv1 -> h1'; tile 5) on the same operands.
+    Rows are pixels: h2 [M, c_mid]; either res [M, depth] (the shortcut tensor) or shortcut = (xp [M, c_xp], wsc_rows [depth][c_xp])
+    folded into conv3's K; W3 [depth][c_mid] and W1 [n2][depth] as filter ROWS; bias3 [depth] or None; pre = (scale, shift) [depth];
+    bn1 = (scale, shift) [n2]; relu1: ReLU on h1' (else only the clamp to the fp16 range).  Activations are float arrays / tensors or
+    split device tensors.
+      res_ld > depth: the pair reads the shortcut out of a buffer with rows of res_ld elements whose extra columns are NaN (the two
+        launches always get it contiguous);
+      guard_rows: every input is followed by that many rows of NaN halves, every output by that many rows of PAIR_SENTINEL -- and the
+        valid rows of the outputs start as PAIR_SENTINEL too, not as zeros;
+      stream: the device tensor of packing.pack_pair_stream([W3 | wsc_rows], W1) if the caller has packed it already (host work);
+      two_launches: build the two hmmr_conv_gemm launches instead of the pair.
+    .descs are the descriptors run() launches (a test may edit them), .trunk / .h1 the split outputs, guard rows included."""
+
+    def __init__(self, h2, W3, bias3, pre, W1, bn1, res=None, shortcut=None, relu1=True, res_ld=0, guard_rows=0, stream=None,
+                 two_launches=False, device="cuda:0"):
+        self.lib = L.load()
+        dev = self.dev = torch.device(device)
+        store = self.store = packing.DeviceStore(dev)
+        X3 = L.HMMR_F16X3
+
+        def rows(x):
+            if isinstance(x, torch.Tensor) and x.is_cuda and x.dtype == torch.int32:
+                return x.contiguous()
+            return packing.to_split(torch.as_tensor(np.asarray(x), dtype=torch.float32).to(dev))
+
+        def guarded(x, ld=0):
+            m_, c = x.shape
+            if not guard_rows and ld <= c:
+                return x
+            buf = torch.full((m_ + guard_rows, max(ld, c)), PAIR_NAN_WORD, dtype=torch.int32, device=dev)
+            buf[:m_, :c] = x
+            return buf
+
+        W3 = np.asarray(W3, np.float32)
+        W1 = np.asarray(W1, np.float32)
+        h2 = guarded(rows(h2))
+        m, cm = h2.shape[0] - guard_rows, h2.shape[1]
+        depth, n2 = W3.shape[0], W1.shape[0]
+        assert W3.shape == (depth, cm) and W1.shape == (n2, depth), (W3.shape, W1.shape)
+        xp = rt = None
+        c_xp = 0
+        if shortcut is not None:
+            xp = guarded(rows(shortcut[0]))
+            c_xp = xp.shape[1]
+            W3 = np.concatenate([W3, np.asarray(shortcut[1], np.float32)], axis=1)
+            assert xp.shape[0] == m + guard_rows and W3.shape == (depth, cm + c_xp)
+        if res is not None:
+            rt = rows(res)
+            assert tuple(rt.shape) == (m, depth)
+            rt = guarded(rt, 0 if two_launches else res_ld)
+        self.m, self.guard_rows = m, guard_rows
+        self.inputs = (h2, xp, rt)
+        k3, k1 = packing.row_pow2(W3), packing.row_pow2(W1)
+        sc3 = store.vec(np.exp2(-k3.astype(np.float64)).astype(np.float32))
+        sc1 = store.vec((np.asarray(bn1[0], np.float64) * np.exp2(-k1.astype(np.float64))).astype(np.float32))
+        b3 = store.vec(bias3) if bias3 is not None else None
+        ps, pb, b1 = store.vec(pre[0]), store.vec(pre[1]), store.vec(bn1[1])
+        self.trunk = torch.full((m + guard_rows, depth), PAIR_SENTINEL, dtype=torch.int32, device=dev)
+        self.h1 = torch.full((m + guard_rows, n2), PAIR_SENTINEL, dtype=torch.int32, device=dev)
+        ptr = lambda t: t.data_ptr() if t is not None else None
+        if two_launches:
+            w3p = store.put(packing.scale_rows(W3, k3), packing.SPLIT)          # [depth][K3] rows, K-contiguous (what hmmr_conv_gemm reads)
+            w1p = store.put(packing.scale_rows(W1, k1), packing.SPLIT)
+            d = L.ConvDesc()
+            d.in_, d.w, d.scale, d.shift, d.out = h2.data_ptr(), w3p.data_ptr(), sc3.data_ptr(), ptr(b3), self.trunk.data_ptr()
+            d.in_dtype = d.out_dtype = X3
+            d.n_img, d.hin, d.win, d.cin = 1, 1, m, cm
+            d.in_img_stride, d.in_row_stride, d.in_px_stride = m * cm, m * cm, cm
+            d.kh = d.kw = d.sy = d.sx = 1
+            d.ho, d.wo, d.cout, d.ldo = 1, m, depth, depth
+            if xp is not None:
+                d.in2, d.cin2 = xp.data_ptr(), c_xp
+            if rt is not None:
+                d.res, d.ldr = rt.data_ptr(), depth
+            d.tile = 5
+            e = L.ConvDesc()
+            e.in_, e.w, e.scale, e.shift, e.out = self.trunk.data_ptr(), w1p.data_ptr(), sc1.data_ptr(), b1.data_ptr(), self.h1.data_ptr()
+            e.in_dtype = e.out_dtype = X3
+            e.n_img, e.hin, e.win, e.cin = 1, 1, m, depth
+            e.in_img_stride, e.in_row_stride, e.in_px_stride = m * depth, m * depth, depth
+            e.kh = e.kw = e.sy = e.sx = 1
+            e.ho, e.wo, e.cout, e.ldo = 1, m, n2, n2
+            e.relu, e.pro_scale, e.pro_shift, e.tile = int(bool(relu1)), ps.data_ptr(), pb.data_ptr(), 5
+            self.descs, self._call, self._what = [d, e], self.lib.hmmr_conv_gemm, "hmmr_conv_gemm (one of the pair's two launches)"
+        else:
+            if stream is None:
+                stream = packing.pack_pair_stream(W3, W1)
+            self.stream = stream.to(dev)
+            assert self.stream.numel() * 2 == self.lib.hmmr_pair_stream_bytes((cm + c_xp) // 16, depth, n2)
+            t = L.TailDesc()
+            t.dtype, t.h2, t.m, t.c_mid, t.depth = X3, h2.data_ptr(), m, cm, depth
+            t.scale3, t.shift3, t.out = sc3.data_ptr(), ptr(b3), self.trunk.data_ptr()
+            if xp is not None:
+                t.xp, t.c_xp = xp.data_ptr(), c_xp
+            if rt is not None:
+                t.res, t.ldr = rt.data_ptr(), rt.shape[1]
+            t.pre_scale, t.pre_shift = ps.data_ptr(), pb.data_ptr()
+            t.scale1, t.shift1, t.relu1, t.n2, t.out_h1 = sc1.data_ptr(), b1.data_ptr(), int(bool(relu1)), n2, self.h1.data_ptr()
+            t.pair_stream = self.stream.data_ptr()
+            self.descs, self._call, self._what = [t], self.lib.hmmr_bottleneck_tail, "hmmr_bottleneck_tail (unit pair)"
+
+    def run(self):
+        """launch on the current stream (no synchronisation: tools time this)"""
+        st = torch.cuda.current_stream(self.dev).cuda_stream
+        for d in self.descs:
+            L.check(self._call(C.byref(d), st), self._what)
+
+
+def unit_pair(h2, W3, bias3, pre, W1, bn1, **kw):
+    """UnitPairCall(...) run once: the split device tensors (trunk [M + guard_rows, depth], h1' [M + guard_rows, n2])."""
+    c = UnitPairCall(h2, W3, bias3, pre, W1, bn1, **kw)
+    c.run()
+    torch.cuda.synchronize(c.dev)
+    return c.trunk, c.h1

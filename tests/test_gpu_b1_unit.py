@@ -5,7 +5,8 @@
   ragged last tile; tiles that straddle images) and through the whole ResNet (slim resnet_v2.bottleneck as invoked at
   /root/reference/src/models.py:65-75, SURVEY App. A);
 * csrc/unit_pair.hip against the two launches IT replaces on ONE batch with the switch of hmmr_resnet50_fwd forced either way
-  (hmmr_debug_t.pair_min_pixels), with the library's launch counters as the proof of which kernel ran.
+  (hmmr_debug_t.pair_min_pixels), with the library's launch counters as the proof of which kernel ran.  The unit-pair kernel ALONE
+  (ragged row counts, persistent-tile geometries, float64, run flags, refusals): tests/test_gpu_unit_pair.py.
 """
 import numpy as np
 import pytest

@@ -29,7 +29,6 @@ print("pair_form %d%s" % (form, "  (%s)" % L.LIB_PATH if ts is not None else "")
 cm, depth, n2, hw, cxp = {"b2": (128, 512, 128, 28, 0), "b3": (256, 1024, 256, 14, 0), "b2f": (128, 512, 128, 28, 256)}[blk]
 m = n * hw * hw
 dev = "cuda"
-X3 = L.HMMR_F16X3
 g = torch.Generator(device="cpu").manual_seed(3)
 rnd = lambda *s: torch.randn(*s, generator=g)
 h2 = packing.to_split(rnd(m, cm).clamp_(min=0).to(dev))
@@ -38,67 +37,13 @@ res = None if cxp else packing.to_split(rnd(m, depth).to(dev))
 K3 = cm + cxp
 W3 = (rnd(depth, K3) / K3 ** 0.5).numpy()
 W1 = (rnd(n2, depth) / depth ** 0.5).numpy()
-b3 = rnd(depth).to(dev)
-ps, pb = (torch.rand(depth, generator=g) + 0.5).to(dev), (rnd(depth) * 0.3).to(dev)
-s1, b1 = (torch.rand(n2, generator=g) + 0.5), (rnd(n2) * 0.3).to(dev)
-store = packing.DeviceStore(dev)
-k3, k1 = packing.row_pow2(W3), packing.row_pow2(W1)
-w3p = store.put(packing.scale_rows(W3, k3), packing.SPLIT)           # [depth][K3] rows, K-contiguous (what hmmr_conv_gemm reads)
-w1p = store.put(packing.scale_rows(W1, k1), packing.SPLIT)
-sc3 = torch.from_numpy(np.exp2(-k3.astype(np.float64)).astype(np.float32)).to(dev)
-sc1 = torch.from_numpy((s1.double().numpy() * np.exp2(-k1.astype(np.float64))).astype(np.float32)).to(dev)
-stream = packing.pack_pair_stream(W3, W1).to(dev)
-assert stream.numel() * 2 == lib.hmmr_pair_stream_bytes(K3 // 16, depth, n2)
-st = torch.cuda.current_stream().cuda_stream
-
-
-def reference():
-    trunk = packing.empty_act((m, depth), X3, dev, zero=True)
-    h1 = packing.empty_act((m, n2), X3, dev, zero=True)
-    d = L.ConvDesc()
-    d.in_, d.w, d.scale, d.shift, d.out = h2.data_ptr(), w3p.data_ptr(), sc3.data_ptr(), b3.data_ptr(), trunk.data_ptr()
-    d.in_dtype = d.out_dtype = X3
-    d.n_img, d.hin, d.win, d.cin = 1, 1, m, cm
-    d.in_img_stride, d.in_row_stride, d.in_px_stride = m * cm, m * cm, cm
-    d.kh = d.kw = d.sy = d.sx = 1
-    d.ho, d.wo, d.cout, d.ldo = 1, m, depth, depth
-    if cxp:
-        d.in2, d.cin2 = xp.data_ptr(), cxp
-    else:
-        d.res, d.ldr = res.data_ptr(), depth
-    d.tile = 5
-    e = L.ConvDesc()
-    e.in_, e.w, e.scale, e.shift, e.out = trunk.data_ptr(), w1p.data_ptr(), sc1.data_ptr(), b1.data_ptr(), h1.data_ptr()
-    e.in_dtype = e.out_dtype = X3
-    e.n_img, e.hin, e.win, e.cin = 1, 1, m, depth
-    e.in_img_stride, e.in_row_stride, e.in_px_stride = m * depth, m * depth, depth
-    e.kh = e.kw = e.sy = e.sx = 1
-    e.ho, e.wo, e.cout, e.ldo = 1, m, n2, n2
-    e.relu, e.pro_scale, e.pro_shift, e.tile = 1, ps.data_ptr(), pb.data_ptr(), 5
-
-    def run():
-        L.check(lib.hmmr_conv_gemm(C.byref(d), st), "conv3")
-        L.check(lib.hmmr_conv_gemm(C.byref(e), st), "conv1'")
-    return trunk, h1, run
-
-
-def pair():
-    trunk = packing.empty_act((m, depth), X3, dev, zero=True)
-    h1 = packing.empty_act((m, n2), X3, dev, zero=True)
-    t = L.TailDesc()
-    t.dtype, t.h2, t.m, t.c_mid, t.depth = X3, h2.data_ptr(), m, cm, depth
-    t.scale3, t.shift3, t.out = sc3.data_ptr(), b3.data_ptr(), trunk.data_ptr()
-    if cxp:
-        t.xp, t.c_xp = xp.data_ptr(), cxp
-    else:
-        t.res, t.ldr = res.data_ptr(), depth
-    t.pre_scale, t.pre_shift = ps.data_ptr(), pb.data_ptr()
-    t.scale1, t.shift1, t.relu1, t.n2, t.out_h1 = sc1.data_ptr(), b1.data_ptr(), 1, n2, h1.data_ptr()
-    t.pair_stream = stream.data_ptr()
-
-    def run():
-        L.check(lib.hmmr_bottleneck_tail(C.byref(t), st), "unit pair")
-    return trunk, h1, run
+b3 = rnd(depth).numpy()
+pre = ((torch.rand(depth, generator=g) + 0.5).numpy(), (rnd(depth) * 0.3).numpy())
+bn1 = ((torch.rand(n2, generator=g) + 0.5).numpy(), (rnd(n2) * 0.3).numpy())
+# engine.UnitPairCall: the kernel alone, and the two hmmr_conv_gemm launches it replaces (tile 5) on the same operands
+kw = dict(res=res, shortcut=(xp, W3[:, cm:]) if cxp else None, device=dev)
+ref_call = engine.UnitPairCall(h2, W3[:, :cm], b3, pre, W1, bn1, two_launches=True, **kw)
+pair_call = engine.UnitPairCall(h2, W3[:, :cm], b3, pre, W1, bn1, **kw)
 
 
 def timed(run, reps=10):
@@ -113,8 +58,8 @@ def timed(run, reps=10):
     return e0.elapsed_time(e1) / reps
 
 
-tr, hr, run_ref = reference()
-tp, hp, run_pair = pair()
+tr, hr, run_ref = ref_call.trunk, ref_call.h1, ref_call.run
+tp, hp, run_pair = pair_call.trunk, pair_call.h1, pair_call.run
 run_ref()
 run_pair()
 torch.cuda.synchronize()
