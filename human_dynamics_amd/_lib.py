@@ -152,6 +152,17 @@ class SmplSource(C.Structure):
                 ("J_regressor", _fp), ("lbs_weights", _fp), ("kp_regressor", _fp), ("parents", _ip)]
 
 
+class VideoPlan(C.Structure):
+    """hmmr_video_plan_t: the sliding-window plan of a whole-video call (csrc/video_plan.cpp; host only)"""
+    _fields_ = [(k, C.c_int) for k in ("n", "T", "fov", "margin", "g", "n_windows", "max_frames", "max_windows", "resnet_passes", "tail_passes")]
+
+
+class Model(C.Structure):
+    """hmmr_model_t: the packed stages of one model, as hmmr_predict_video reads them"""
+    _fields_ = [("resnet", C.POINTER(ResnetWeights)), ("temporal", C.POINTER(TemporalWeights)), ("hallucinator", C.POINTER(HallucinatorWeights)),
+                ("ief", C.POINTER(IefWeights)), ("smpl", C.POINTER(SmplConsts)), ("sequence_length", C.c_int), ("fov", C.c_int)]
+
+
 RENDER_MAX_FRAMES, RENDER_MIN_SIZE, RENDER_MAX_SIZE, RENDER_MAX_FACES = 4096, 16, 1024, 65536
 RENDER_BG_COLOR, RENDER_BG_FLOAT, RENDER_BG_FRAME = 0, 1, 2
 # hmmr_track_* (csrc/track.hip): limits, the gap scan's step, the status bits of hmmr_track_crop_geom
@@ -278,6 +289,13 @@ SIGNATURES = {
                                         _vp, C.c_size_t, _vp]),
     "hmmr_smpl_fwd_strided": (C.c_int, [C.POINTER(SmplConsts), _fp, C.c_int, _fp, C.c_int, _fp, C.c_int, C.c_int,
                                         _fp, _fp, _fp, _fp, C.c_int64, _vp, C.c_size_t, _vp]),
+    "hmmr_video_plan": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(VideoPlan)]),
+    "hmmr_record_layout": (C.c_int, [C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int32), C.POINTER(C.c_int64)]),
+    "hmmr_gather_windows": (C.c_int, [_fp, C.c_int, _fp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _fp, _vp]),
+    "hmmr_keep_rows": (C.c_int, [_fp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _fp, C.c_int64, _vp]),
+    "hmmr_predict_video_workspace_bytes": (C.c_size_t, [C.POINTER(Model), C.c_int, C.c_int, C.c_int]),
+    "hmmr_predict_video": (C.c_int, [C.POINTER(Model), _fp, C.c_int, _fp, C.c_int64, C.POINTER(C.c_int32), C.c_int, C.c_int,
+                                     _vp, C.c_size_t, _vp]),
 }
 
 _lib = None

@@ -1,0 +1,168 @@
+// hmmr_predict_video (include/hmmr_hip.h): Tester.predict_all_images (src/evaluation/tester.py:260-312) as ONE call of the C ABI -- the
+// frames of a video on the device in, the packed per-frame records on the device out, no Python and no torch in between.  The call
+// only sequences the stage entry points on the caller's stream: ResNet passes into phi, then per tail pass gather -> f_movie (or the
+// hallucinator) -> keep -> IEF -> SMPL records.  It owns no kernel and makes no HIP call itself; every check that a stage would make
+// is made here first, for every pass, so that a refused call has queued nothing.
+#include <stddef.h>
+#include <stdint.h>
+
+#include <initializer_list>
+
+#include "hmmr_hip.h"
+
+void hmmr_set_error(const char* fmt, ...);
+
+#define VIDEO_REQUIRE(cond, ...) do { if (!(cond)) { hmmr_set_error(__VA_ARGS__); return -1; } } while (0)
+
+namespace {
+
+constexpr int C = 2048;                  // feature width (phi, movie strips)
+inline size_t align_up(size_t v) { return (v + 255) & ~(size_t)255; }
+inline int imin(int a, int b) { return a < b ? a : b; }
+
+// the carve of `ws`: phi, then ONE region that first serves the ResNet passes and afterwards the tail passes (same stream: in order)
+struct Carve {
+    size_t phi, region;                                  // offsets
+    size_t resnet_bytes;                                 // inside the region, from its start
+    size_t windows, strips, kept, omegas, movie_ws, ief_ws, smpl_ws;      // offsets inside the region
+    size_t movie_bytes, ief_bytes, smpl_bytes;
+    size_t total;
+};
+
+struct TailPass { int w0, nw, o0, keep; };
+inline TailPass tail_pass(const hmmr_video_plan_t& p, int i) {
+    TailPass t;
+    t.w0 = i * p.max_windows;                            // (i < tail_passes: w0 < n_windows, no overflow)
+    t.nw = imin(p.max_windows, p.n_windows - t.w0);
+    const long long o0 = (long long)t.w0 * p.g, o1 = (long long)(t.w0 + t.nw) * p.g;
+    t.o0 = (int)o0;
+    t.keep = (int)((o1 < p.n ? o1 : (long long)p.n) - o0);
+    return t;
+}
+inline int resnet_pass_frames(const hmmr_video_plan_t& p, int i) { return imin(p.max_frames, p.n - i * p.max_frames); }
+
+// model pointers and everything the stages would refuse that does not depend on the frame count
+int check_model(const hmmr_model_t* m, const char* who) {
+    VIDEO_REQUIRE(m && m->resnet && m->ief && m->smpl, "%s: null model, resnet, ief or smpl", who);
+    VIDEO_REQUIRE(!m->temporal != !m->hallucinator, "%s: exactly one of temporal ('pred') and hallucinator ('hal') must be set", who);
+    for (int dt : {m->resnet->dtype, m->temporal ? m->temporal->dtype : m->hallucinator->dtype, m->ief->dtype})
+        VIDEO_REQUIRE(dt == HMMR_F32 || dt == HMMR_BF16 || dt == HMMR_F16X3, "%s: bad dtype %d", who, dt);
+    VIDEO_REQUIRE(m->resnet->unit[0].c_in == 64 && m->resnet->unit[HMMR_RESNET_UNITS - 1].depth == C, "%s: bad ResNet unit table", who);
+    VIDEO_REQUIRE(!m->temporal || (m->temporal->num_blocks >= 1 && m->temporal->num_blocks <= HMMR_MAX_TEMPORAL_BLOCKS),
+                  "%s: bad temporal num_blocks", who);
+    const hmmr_ief_weights_t* w = m->ief;
+    VIDEO_REQUIRE(w->num_regressors >= 1 && w->num_regressors <= HMMR_MAX_REGRESSORS, "%s: bad ief num_regressors", who);
+    for (int r = 0; r < w->num_regressors; ++r) {
+        const int nd = r == 0 ? 85 : (w->no_optcam ? 75 : 72);
+        VIDEO_REQUIRE(w->reg[r].nd == nd, "%s: ief regressor %d has nd=%d (expected %d)", who, r, w->reg[r].nd, nd);
+    }
+    const hmmr_smpl_consts_t* s = m->smpl;
+    VIDEO_REQUIRE(s->num_verts >= 1 && s->num_kps >= 1 && s->lbs_nnz >= 1 && s->lbs_nnz <= 24, "%s: bad SMPL constants (num_verts=%d, num_kps=%d, lbs_nnz=%d)",
+                  who, s->num_verts, s->num_kps, s->lbs_nnz);
+    VIDEO_REQUIRE(s->vpad % 128 == 0 && s->vpad >= s->num_verts, "%s: SMPL vpad=%d must be a multiple of 128 covering num_verts=%d", who, s->vpad,
+                  s->num_verts);
+    return 0;
+}
+
+// n > 0.  The sizes of the first and of the last pass bound every pass between them (all but the last are full).
+int carve(const hmmr_model_t* m, const hmmr_video_plan_t& p, Carve* out) {
+    Carve c = {};
+    const int R = m->ief->num_regressors;
+    size_t off = 0;
+    c.phi = off; off += align_up((size_t)(p.n + 1) * C * 4);
+    c.region = off;
+    c.resnet_bytes = hmmr_resnet50_workspace_bytes(imin(p.n, p.max_frames) + 1, m->resnet->dtype);
+    VIDEO_REQUIRE(c.resnet_bytes > 0, "hmmr_predict_video: no ResNet workspace for this dtype");
+    const int mw = imin(p.n_windows, p.max_windows);
+    const TailPass first = tail_pass(p, 0), last = tail_pass(p, p.tail_passes - 1);
+    const int mk = first.keep > last.keep ? first.keep : last.keep;
+    size_t t = 0;
+    c.windows = t; t += align_up((size_t)mw * p.T * C * 4);
+    c.strips = t;  t += align_up((size_t)mw * p.T * C * 4);
+    c.kept = t;    t += align_up((size_t)mk * C * 4);
+    c.omegas = t;  t += align_up((size_t)R * mk * 85 * 4);
+    auto movie = [&](int nw) { return m->temporal ? hmmr_temporal_workspace_bytes(nw, p.T, m->temporal->dtype)
+                                                  : hmmr_hallucinator_workspace_bytes(nw * p.T, m->hallucinator->dtype); };
+    auto max2 = [](size_t a, size_t b) { return a > b ? a : b; };
+    c.movie_bytes = max2(movie(first.nw), movie(last.nw));
+    c.ief_bytes = max2(hmmr_ief_workspace_bytes(first.keep, R, m->ief->dtype), hmmr_ief_workspace_bytes(last.keep, R, m->ief->dtype));
+    c.smpl_bytes = max2(hmmr_smpl_workspace_bytes(R * first.keep), hmmr_smpl_workspace_bytes(R * last.keep));
+    VIDEO_REQUIRE(c.movie_bytes && c.ief_bytes && c.smpl_bytes, "hmmr_predict_video: a stage reports no workspace for this model");
+    c.movie_ws = t; t += align_up(c.movie_bytes);
+    c.ief_ws = t;   t += align_up(c.ief_bytes);
+    c.smpl_ws = t;  t += align_up(c.smpl_bytes);
+    c.total = c.region + (t > align_up(c.resnet_bytes) ? t : align_up(c.resnet_bytes));
+    *out = c;
+    return 0;
+}
+
+}  // namespace
+
+extern "C" size_t hmmr_predict_video_workspace_bytes(const hmmr_model_t* model, int n, int max_frames, int max_windows) {
+    hmmr_video_plan_t p;
+    if (check_model(model, "hmmr_predict_video_workspace_bytes") || hmmr_video_plan(n, model->sequence_length, model->fov, max_frames, max_windows, &p))
+        return 0;
+    Carve c;
+    if (p.n == 0) p.n = 1, p.n_windows = p.resnet_passes = p.tail_passes = 1;      // (an empty video needs nothing: report what one frame takes, never 0 for a good model)
+    return carve(model, p, &c) ? 0 : c.total;
+}
+
+extern "C" int hmmr_predict_video(const hmmr_model_t* model, const float* images, int n, float* rec, int64_t ld_rec,
+                                  const int32_t* field_offsets, int max_frames, int max_windows, void* ws, size_t ws_bytes,
+                                  void* stream) {
+    if (check_model(model, "hmmr_predict_video")) return -1;
+    hmmr_video_plan_t p;
+    if (hmmr_video_plan(n, model->sequence_length, model->fov, max_frames, max_windows, &p)) return -1;
+    VIDEO_REQUIRE(field_offsets, "hmmr_predict_video: null field_offsets");
+    const int R = model->ief->num_regressors;
+    {   // the record: every field of every container ends inside it
+        const int64_t K = model->smpl->num_kps, V = model->smpl->num_verts;
+        const int64_t size[7] = {3, 3 * K, 2 * K, 24 * 9, 10, 3 * V, 85};
+        for (int r = 0; r < R; ++r)
+            for (int f = 0; f < 7; ++f) {
+                const int64_t o = field_offsets[r * 7 + f];
+                VIDEO_REQUIRE(o >= 0 && o + size[f] <= ld_rec, "hmmr_predict_video: field %d of container %d (offset %lld, %lld floats) does not fit ld_rec=%lld",
+                              f, r, (long long)o, (long long)size[f], (long long)ld_rec);
+            }
+    }
+    if (n == 0) return 0;
+    VIDEO_REQUIRE(images && rec && ws, "hmmr_predict_video: null images, rec or ws");
+    VIDEO_REQUIRE(((uintptr_t)ws & 255u) == 0, "hmmr_predict_video: ws must be 256-byte aligned");
+    Carve c;
+    if (carve(model, p, &c)) return -1;
+    VIDEO_REQUIRE(ws_bytes >= c.total, "hmmr_predict_video: workspace too small (%zu < %zu)", ws_bytes, c.total);
+    {   // the unit table against both pass sizes the ResNet will see (hmmr_resnet50_plan: host only)
+        hmmr_unit_plan_t units[HMMR_RESNET_UNITS];
+        if (hmmr_resnet50_plan(model->resnet, resnet_pass_frames(p, p.resnet_passes - 1) + 1, units)) return -1;
+        if (p.resnet_passes > 1 && hmmr_resnet50_plan(model->resnet, p.max_frames, units)) return -1;
+    }
+
+    char* base = (char*)ws;
+    float* phi = (float*)(base + c.phi);
+    char* region = base + c.region;
+    for (int i = 0; i < p.resnet_passes; ++i) {
+        const int f0 = i * p.max_frames, nf = resnet_pass_frames(p, i), n_zero = i == p.resnet_passes - 1;
+        if (hmmr_resnet50_fwd(model->resnet, images + (size_t)f0 * 224 * 224 * 3, nf, n_zero, phi + (size_t)f0 * C, region, c.resnet_bytes,
+                              stream, nullptr))
+            return -2;
+    }
+    float* windows = (float*)(region + c.windows);
+    float* strips = (float*)(region + c.strips);
+    float* kept = (float*)(region + c.kept);
+    float* omegas = (float*)(region + c.omegas);
+    for (int i = 0; i < p.tail_passes; ++i) {
+        const TailPass t = tail_pass(p, i);
+        if (hmmr_gather_windows(phi, p.n, phi + (size_t)p.n * C, t.w0, t.nw, p.T, p.margin, p.g, C, windows, stream)) return -2;
+        if (model->temporal) {
+            if (hmmr_temporal_fwd(model->temporal, windows, t.nw, p.T, strips, region + c.movie_ws, c.movie_bytes, stream)) return -2;
+        } else if (hmmr_hallucinator_fwd(model->hallucinator, windows, t.nw * p.T, strips, region + c.movie_ws, c.movie_bytes, stream)) {
+            return -2;
+        }
+        if (hmmr_keep_rows(strips, t.w0, t.nw, p.T, p.margin, p.g, C, p.n, kept, C, stream)) return -2;
+        if (hmmr_ief_fwd(model->ief, kept, t.keep, omegas, region + c.ief_ws, c.ief_bytes, stream)) return -2;
+        if (hmmr_smpl_fwd_records(model->smpl, omegas, R, t.keep, rec + (size_t)t.o0 * (size_t)ld_rec, ld_rec, field_offsets,
+                                  region + c.smpl_ws, c.smpl_bytes, stream))
+            return -2;
+    }
+    return 0;
+}

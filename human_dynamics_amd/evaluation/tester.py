@@ -429,6 +429,59 @@ class Tester(object):
         torch.cuda.synchronize(self.engine.device)
         return {k: v.float().cpu().numpy() for k, v in out.items() if want is None or k in want}
 
+    def native_model(self):
+        """hmmr_model_t over the engine's already-packed structs (they stay owned by the engine): what hmmr_predict_video and its
+        workspace query read.  pred_mode picks the f_movie form: the temporal encoder or the hallucinator, never both."""
+        import ctypes as C
+        eng = self.engine
+        eng._need(eng.rw, "resnet_v2_50/*")
+        eng._need(eng.iw, "single_view_ief*/3D_module/* and mean_param")
+        eng._need(eng.sc, "SMPL")
+        model = L.Model()
+        model.resnet, model.ief, model.smpl = C.pointer(eng.rw), C.pointer(eng.iw), C.pointer(eng.sc)
+        if self.pred_mode == "pred":
+            eng._need(eng.tw, "AZ_FC_block*")
+            model.temporal = C.pointer(eng.tw)
+        else:
+            eng._need(eng.hw, "fc2_res/*")
+            model.hallucinator = C.pointer(eng.hw)
+        model.sequence_length, model.fov = self.sequence_length, self.fov
+        return model
+
+    def predict_all_images_native(self, all_images, want=None, max_frames=MAX_DEVICE_FRAMES, max_windows=MAX_TAIL_WINDOWS):
+        """`predict_all_images` through the library's own whole-video call (hmmr_predict_video, include/hmmr_hip.h): the ResNet
+        passes, the window gather, f_movie, the kept rows, IEF and SMPL are queued by ONE C call on the engine's already-packed
+        structs -- what a caller without Python and torch runs (tests/c_abi/predict_video.c).  Same dict, same bytes.
+        all_images: [N,224,224,3] float32 in [-1,1], host or device.  max_frames / max_windows: frames per ResNet pass and
+        windows per tail pass; they bound the workspace and change no bit."""
+        import ctypes as C
+        from ..dist import unpack_outputs
+        from ..engine import _Workspace
+        max_frames, max_windows = int(max_frames), int(max_windows)
+
+        def run():
+            eng = self.engine
+            model = self.native_model()
+            frames = eng.to_device(all_images)
+            n = frames.shape[0]
+            assert n == 0 or tuple(frames.shape[1:]) == (224, 224, 3), frames.shape
+            R = eng.iw.num_regressors
+            offs, ld_rec = (C.c_int32 * (R * 7))(), C.c_int64(0)
+            L.check(eng.lib.hmmr_record_layout(eng.num_kps, eng.num_verts, R, offs, C.byref(ld_rec)), "hmmr_record_layout")
+            layout, rec_len = self.record_layout()
+            assert rec_len == ld_rec.value, (rec_len, ld_rec.value)
+            rec = torch.empty((n, rec_len), dtype=torch.float32, device=eng.device)
+            nbytes = eng.lib.hmmr_predict_video_workspace_bytes(C.byref(model), n, max_frames, max_windows)
+            if not nbytes:
+                L.check(-1, "hmmr_predict_video_workspace_bytes")
+            ws = eng._ws.setdefault("video", _Workspace(eng.device)).get(nbytes)
+            L.check(eng.lib.hmmr_predict_video(C.byref(model), frames.data_ptr() if n else None, n, rec.data_ptr() if n else None,
+                                               rec_len, offs, max_frames, max_windows, ws.data_ptr(), nbytes, eng._stream()),
+                    "hmmr_predict_video")
+            torch.cuda.synchronize(eng.device)
+            return {k: v.float().cpu().numpy() for k, v in unpack_outputs(rec, layout).items() if want is None or k in want}
+        return self._guard_saturation(run)
+
     def predict_videos(self, videos, want=None):
         """`predict_all_images` for several videos at once -- how the demo is driven, one call per person track
         (/root/reference/demo_video.py:172, src/evaluation/tester.py:229-312): a list of host arrays [N_i,224,224,3] (float32 in

@@ -874,6 +874,81 @@ size_t hmmr_pack_smpl_bytes(const hmmr_smpl_source_t* src, int lsp, int split);
 int hmmr_pack_smpl(const hmmr_smpl_source_t* src, int lsp, int split, void* host_blob, size_t blob_bytes, const void* device_base,
                    hmmr_smpl_consts_t* out);
 
+/* ------------------------------------------------------------------------- *
+ * A whole video through one call (additive to ABI 19): Tester.predict_all_images (src/evaluation/tester.py:260-312).
+ *
+ * The reference pads the video with `margin` zero IMAGES in front and `num_fill` behind, cuts windows of T frames every
+ * g = T - 2 margin frames (margin = (fov - 1) / 2), runs each through the graph and keeps the centre g predictions of each
+ * (tester.py:281-311).  That scheme is part of the numerical contract -- GroupNorm statistics span the window, the padding
+ * frames pass through the encoder -- so it lives here, not in the binder: window w, slot t sits at padded position
+ * p = w g + t and holds frame p - margin when 0 <= p - margin < n, else the zero image; slot margin + j of window w
+ * (0 <= j < g) is output frame w g + j.
+ *
+ * `batch_size` is not a parameter.  The reference runs count * batch_size windows, count = ceil(n / (g batch_size)); the
+ * windows from ceil(n / g) on keep no frame (their centre slots lie at or beyond frame n), and every stage after the
+ * encoder works per window, so they change no kept value: n_windows = ceil(n / g) here, whatever the caller's batch size.
+ * ------------------------------------------------------------------------- */
+typedef struct {
+    int n, T, fov;               /* as given */
+    int margin, g;               /* (fov - 1) / 2, T - 2 margin */
+    int n_windows;               /* ceil(n / g) */
+    int max_frames, max_windows; /* as given */
+    int resnet_passes;           /* ceil(n / max_frames): pass i encodes frames [i max_frames, min(n, (i + 1) max_frames)); the
+                                    last one carries the zero image (n_zero = 1) */
+    int tail_passes;             /* ceil(n_windows / max_windows): pass i runs windows [i max_windows, min(n_windows, ...)) */
+} hmmr_video_plan_t;
+/* Host only, no HIP call (tester.py:281-289).  Refused (-1): fov even or < 1, g < 1, n < 0, max_frames < 1, max_windows < 1.
+ * n = 0: no window, no pass. */
+int hmmr_video_plan(int n, int T, int fov, int max_frames, int max_windows, hmmr_video_plan_t* out);
+
+/* Host only: the packed per-frame record of make_fetch_dict (tester.py:216-227) as hmmr_smpl_fwd_records reads it.
+ * field_offsets [num_containers][7] (float offsets of cams [3], joints [K,3], kps [K,2], poses [24,3,3], shapes [10], verts
+ * [V,3], omegas [85]): container 0 (the present) first, field after field; then every `_delta` field as
+ * [num_containers - 1][...], container r at index r - 1.  *ld_rec = the record's length in floats.  Either output may be
+ * NULL. */
+int hmmr_record_layout(int num_kps, int num_verts, int num_containers, int32_t* field_offsets, int64_t* ld_rec);
+
+/* The two copies of the scheme (csrc/windows.hip), exposed for tests like hmmr_groupnorm_relu.  Pure copies in 16-byte
+ * pieces (c % 4 == 0, 16-byte aligned pointers), 64-bit offsets, no atomics, nothing allocated; bad arguments are refused
+ * before the launch.  n = 0 (n_total = 0) or n_windows = 0: nothing is launched, 0 is returned.
+ * hmmr_gather_windows (tester.py:285-305): phi [n][c] fp32, phi_zero [c] (the feature of the all-zero image) ->
+ *   out [n_windows][T][c], windows w0 .. w0 + n_windows - 1.
+ * hmmr_keep_rows (tester.py:306-311): strips [n_windows][T][c] of the same windows -> for 0 <= j < g, slot margin + j of
+ *   window w is frame f = w g + j and goes to out + (f - w0 g) ld_out if f < n_total (ld_out >= c, ld_out % 4 == 0); rows
+ *   with f >= n_total and the columns c .. ld_out - 1 are not touched. */
+int hmmr_gather_windows(const float* phi, int n, const float* phi_zero, int w0, int n_windows, int T, int margin, int g,
+                        int c, float* out, void* stream);
+int hmmr_keep_rows(const float* strips, int w0, int n_windows, int T, int margin, int g, int c, int n_total, float* out,
+                   int64_t ld_out, void* stream);
+
+typedef struct {
+    const hmmr_resnet_weights_t* resnet;
+    const hmmr_temporal_weights_t* temporal;          /* pred_mode 'pred' (tester.py:183-188) ... */
+    const hmmr_hallucinator_weights_t* hallucinator;  /* ... or 'hal' (:189-190): exactly one of the two */
+    const hmmr_ief_weights_t* ief;
+    const hmmr_smpl_consts_t* smpl;
+    int sequence_length, fov;                         /* 20, 4 * num_conv_layers + 1 (tester.py:44-47) */
+} hmmr_model_t;
+
+/* hmmr_predict_video: images [n,224,224,3] fp32 in [-1,1] on the device -> rec [n][ld_rec], the packed record of every
+ * frame (hmmr_record_layout, or any layout hmmr_smpl_fwd_records accepts: field_offsets is a HOST array
+ * [ief->num_regressors][7]).  Everything is queued on `stream`; nothing is allocated or synchronised.  Model pointers, the
+ * plan, every unit table, ws_bytes and ld_rec against the end of the last field are checked BEFORE the first launch: a
+ * refused call (-1) queues nothing.  n = 0: returns 0, queues nothing.
+ *   1. ResNet passes of at most max_frames frames (hmmr_resnet50_fwd, one launch sequence each) into phi [n + 1][2048]
+ *      inside `ws`; the last pass appends the zero image (n_zero = 1), whose feature fills every padding slot;
+ *   2. tail passes of at most max_windows windows: hmmr_gather_windows, hmmr_temporal_fwd (or hmmr_hallucinator_fwd over
+ *      the n_windows T slots), hmmr_keep_rows, hmmr_ief_fwd on the kept rows, hmmr_smpl_fwd_records into rec + o0 ld_rec
+ *      (o0 = the pass's first frame).
+ * Per-frame encoder, per-window tail, split_k never chosen from the batch: the records do not depend on max_frames /
+ * max_windows, bit for bit.  The call reads no run flags: read hmmr_run_flags where the records are read.
+ * The workspace (0: bad model or plan) holds phi and, one after the other on the stream, the ResNet workspace of
+ * min(n, max_frames) + 1 frames and the tail's buffers for min(n_windows, max_windows) windows; it never shrinks as n grows. */
+size_t hmmr_predict_video_workspace_bytes(const hmmr_model_t* model, int n, int max_frames, int max_windows);
+int hmmr_predict_video(const hmmr_model_t* model, const float* images, int n, float* rec, int64_t ld_rec,
+                       const int32_t* field_offsets, int max_frames, int max_windows, void* ws, size_t ws_bytes,
+                       void* stream);
+
 #ifdef __cplusplus
 }
 #endif
