@@ -255,6 +255,7 @@ SIGNATURES = {
     "hmmr_smpl_fwd": (C.c_int, [C.POINTER(SmplConsts), _fp, C.c_int, _fp, C.c_int, _fp, C.c_int, C.c_int,
                                 _fp, _fp, _fp, _fp, _vp, C.c_size_t, _vp]),
     "hmmr_crop_frames": (C.c_int, [_vp, _ip, C.c_int, C.c_int, C.c_int, _fp, _vp]),
+    "hmmr_tube_augment": (C.c_int, [_vp, C.c_int, C.c_int, C.c_int, C.c_int, _ip, _vp, _fp, C.c_int, _fp, _vp]),
     "hmmr_track_workspace_bytes": (C.c_size_t, [C.c_int, C.c_int]),
     "hmmr_track_bbox": (C.c_int, [_fp, _vp, C.POINTER(C.c_int32), C.c_int, C.c_int, C.c_double, C.c_int, C.POINTER(C.c_double), C.c_int,
                                   _fp, _fp, _ip, _vp, C.c_size_t, _vp]),

@@ -17,6 +17,17 @@ __device__ __forceinline__ void taps(int d, int src, int dst, int& s0, int& s1, 
     w0 = (double)(1.0f - f); w1 = (double)f;
 }
 
+// TF 1.8 ResizeBilinear's taps (align_corners=False) along one axis for destination index d of a src -> dst resize:
+// NO half-pixel offset, all float32 -- in = d * (src / dst), lo = (int)in, hi = min(lo + 1, src - 1), lerp = in - lo.
+// The caller interpolates lo + (hi - lo) * lerp.  The clamp of lo changes nothing for 0 <= d < dst (in < src there);
+// it keeps the reads inside the frame when a caller hands over a row that is not a size.
+__device__ __forceinline__ void tf_taps(int d, int src, int dst, int& lo, int& hi, float& lerp) {
+    const float in = (float)d * ((float)src / (float)dst);
+    lo = max(min((int)in, src - 1), 0);
+    hi = min(lo + 1, src - 1);
+    lerp = in - (float)lo;
+}
+
 struct FrameCam { float s, tx, ty; };
 
 // The weak-perspective camera [s, tx, ty] moved from the 224x224 crop to the squared (possibly down-scaled) original

@@ -543,6 +543,37 @@ int hmmr_crop_frames(const unsigned char* frames, const int32_t* geom, int n, in
                      float* out, void* stream);
 
 /* ------------------------------------------------------------------------- *
+ * Tube augmentation in front of the feature extractor (csrc/tube.hip): the pixel side of
+ * TubePreprocessor.preprocess_image (src/util/tube_augmentation.py:114-186; jitter_scale, pad_image_edge, rotate_img,
+ * flip_image, rescale_image of src/util/data_utils.py) as one gather kernel.  images [n,h,w,3] on the device, float32 in
+ * [0,1] (images_are_u8 == 0) or uint8 (!= 0: byte b is read as (float)((double)b / 255.0), a 256-entry table, so both
+ * routes see the same values) -> out [n,S,S,3] float32 in [-1,1].  All operands are DEVICE memory, written by the host
+ * mirror (util/tube_augmentation.py):
+ *   geom [n][4] int32 = {newH, newW, x0, y0}: the size of the frame's scaled image and the scaled-image coordinates of crop
+ *     pixel (0,0) (centre - S/2 after jitter and scaling; may be negative or beyond the image: the edge pad);
+ *   flip [n] bytes: != 0 reverses the frame's columns;  rot [n][6] float32 or NULL: the output -> input transform.
+ * Everything is float32 and evaluated exactly as written, left to right, without contraction:
+ *   crop pixel (x, y): u = clamp(x0 + x, 0, newW - 1), v = clamp(y0 + y, 0, newH - 1) (the clamp is the edge pad); its value is
+ *     the TF 1.8 ResizeBilinear sample (align_corners=False, no half-pixel offset) of the frame at (u, v).  Along an axis
+ *     of source size src and scaled size dst: in = (float)i * ((float)src / (float)dst), lo = (int)in,
+ *     hi = min(lo + 1, src - 1), lerp = in - lo.  top = tl + (tr - tl) * xlerp, bot = bl + (br - bl) * xlerp,
+ *     value = top + (bot - top) * ylerp.
+ *   rot != NULL (tf.contrib.image.rotate(..., 'BILINEAR'); chosen when the preprocessor has rotate_max != 0): output pixel
+ *     (x, y) reads fx = a0 * x + a1 * y + a2, fy = b0 * x + b1 * y + b2 with the row [a0 a1 a2 b0 b1 b2] =
+ *     [cos, -sin, xoff, sin, cos, yoff], xoff = ((S-1) - (cos (S-1) - sin (S-1))) / 2, yoff = ((S-1) - (sin (S-1) + cos (S-1))) / 2.
+ *     xf = floor(fx), xc = xf + 1, likewise y; row_f = (xc - fx) v(yf, xf) + (fx - xf) v(yf, xc), row_c the same on yc,
+ *     value = (yc - fy) row_f + (fy - yf) row_c.  A tap outside [0, S) reads 0.0; a tap inside is the crop pixel above.
+ *   flip (tf.reverse(image, [1]), after the rotation): output column x takes column S - 1 - x.
+ *   last: (value - 0.5f) * 2.0f.
+ * These rules restate the published TF 1.8 kernels (resize_bilinear_op.cc, contrib/image/kernels/image_ops.h); their
+ * agreement with a TensorFlow binary is unmeasured.  Nothing is allocated; bad arguments (null images / geom / flip / out,
+ * n, h, w or S <= 0) are refused before any launch (-1, hmmr_last_error()).  A geom row that is not a size cannot make
+ * the kernel read outside the frame (its taps are clamped), only produce meaningless pixels: the mirror refuses such rows.
+ * ------------------------------------------------------------------------- */
+int hmmr_tube_augment(const void* images, int images_are_u8, int n, int h, int w, const int32_t* geom,
+                      const unsigned char* flip, const float* rot, int S, float* out, void* stream);
+
+/* ------------------------------------------------------------------------- *
  * Track front end (csrc/track.hip): from a person track's 2D keypoints to the geom rows hmmr_crop_frames reads, without a
  * host step.  Replaces src/util/smooth_bbox.py (get_smooth_bbox_params :10-34, kp_to_bbox_param :37-61, get_all_bbox_params
  * :64-105, smooth_bbox_params :108-123) and the per-frame arithmetic of demo_video.predict_on_tracks :136-153 with
