@@ -76,6 +76,11 @@ class LaunchCounts(C.Structure):
                 ("conv1x1_stream", C.c_ulonglong)]
 
 
+class StemCounts(C.Structure):
+    """hmmr_stem_counts_t: the stem's launches since the last clear (one pass: fused OR fused_conv1, or repack + gemm + pool)."""
+    _fields_ = [(k, C.c_ulonglong) for k in ("fused", "fused_conv1", "repack", "gemm", "pool")]
+
+
 class Layer(C.Structure):
     _fields_ = [("w", _vp), ("scale", _fp), ("shift", _fp), ("tile", C.c_int), ("k_order", C.c_int)]
 
@@ -237,11 +242,14 @@ SIGNATURES = {
     "hmmr_set_debug": (None, [C.POINTER(Debug)]),
     "hmmr_get_debug": (None, [C.POINTER(Debug)]),
     "hmmr_launch_counts": (None, [C.POINTER(LaunchCounts), C.c_int]),
+    "hmmr_stem_launch_counts": (None, [C.POINTER(StemCounts), C.c_int]),
     "hmmr_conv_gemm": (C.c_int, [C.POINTER(ConvDesc), _vp]),
     "hmmr_conv_splitk_workspace_bytes": (C.c_size_t, [C.c_int, C.c_int, C.c_int]),
     "hmmr_resnet50_workspace_bytes": (C.c_size_t, [C.c_int, C.c_int]),
     "hmmr_resnet50_fwd": (C.c_int, [C.POINTER(ResnetWeights), _fp, C.c_int, C.c_int, _fp, _vp, C.c_size_t, _vp,
                                     C.POINTER(C.c_float)]),
+    "hmmr_resnet50_stem_workspace_bytes": (C.c_size_t, [C.POINTER(ResnetWeights), C.c_int]),
+    "hmmr_resnet50_stem": (C.c_int, [C.POINTER(ResnetWeights), _fp, C.c_int, C.c_int, _vp, _vp, C.POINTER(C.c_int), _vp, C.c_size_t, _vp]),
     "hmmr_resnet50_plan": (C.c_int, [C.POINTER(ResnetWeights), C.c_int, C.POINTER(UnitPlan)]),
     "hmmr_temporal_workspace_bytes": (C.c_size_t, [C.c_int, C.c_int, C.c_int]),
     "hmmr_temporal_fwd": (C.c_int, [C.POINTER(TemporalWeights), _fp, C.c_int, C.c_int, _fp, _vp, C.c_size_t, _vp]),
@@ -337,6 +345,13 @@ def launch_counts(clear=False):
     c = LaunchCounts()
     load().hmmr_launch_counts(C.byref(c), int(bool(clear)))
     return {k: int(getattr(c, k)) for k, _ in LaunchCounts._fields_}
+
+
+def stem_launch_counts(clear=False):
+    """{fused, fused_conv1, repack, gemm, pool: the stem's launches since the last clear} (hmmr_stem_launch_counts)."""
+    c = StemCounts()
+    load().hmmr_stem_launch_counts(C.byref(c), int(bool(clear)))
+    return {k: int(getattr(c, k)) for k, _ in StemCounts._fields_}
 
 
 def check(rc, what=""):

@@ -208,8 +208,24 @@ static bool stem_unfused(const hmmr_resnet_weights_t* w, const hmmr_debug_t* dbg
 // fragment-major copy of the conv1 filters (hmmr_resnet_unit_t.conv1_frag, round 5)
 static bool stem_writes_conv1(const hmmr_resnet_weights_t* w, const hmmr_debug_t* dbg) {
     const hmmr_resnet_unit_t& U0 = w->unit[0];
-    return !stem_unfused(w, dbg) && !dbg->stem_no_conv1 && (w->dtype == HMMR_BF16 || (w->dtype == HMMR_F16X3 && U0.conv1_frag)) &&
+    return !stem_unfused(w, dbg) && !dbg->stem_no_conv1 && ((w->dtype == HMMR_BF16 && U0.conv1.w) || (w->dtype == HMMR_F16X3 && U0.conv1_frag)) &&
            !U0.sc_c1.w && U0.c_in == 64 && U0.base == 64 && U0.conv1.scale && U0.conv1.shift;
+}
+
+// What both stem routes need of the table and of the image pointer, checked BEFORE anything is queued (hmmr_resnet50_fwd and
+// hmmr_resnet50_stem).  The fused kernels read the image as aligned 16-byte groups of 4 floats (image rows and images are multiples of 16
+// bytes), so a pointer that is not is refused -- on the three-kernel route too: a route switch never changes what a caller may pass.
+// The template (bf16 / fp32) form of the fused kernel has no per-channel scale of the filter rows; the three-kernel route applies
+// stem.scale in hmmr_conv_gemm's epilogue.  A table with one would make the routes disagree silently, so the fused route refuses it
+// (the shipped packers leave stem.scale NULL in these modes; f16x3 carries the pack-time row scale there and both routes apply it).
+static int stem_check(const hmmr_resnet_weights_t* w, const float* images, const hmmr_debug_t* dbg, const char* who) {
+    const hmmr_resnet_unit_t& U0 = w->unit[0];
+    HMMR_REQUIRE(w->stem.w && w->stem.shift && U0.pre_scale && U0.pre_shift, "%s: null argument (stem filters / bias, block1/unit_1 preact)", who);
+    HMMR_REQUIRE(((uintptr_t)images & 15u) == 0, "%s: images must be 16-byte aligned (%p is not)", who, (const void*)images);
+    HMMR_REQUIRE(stem_unfused(w, dbg) || w->dtype == HMMR_F16X3 || !w->stem.scale,
+                 "%s: the fused %s stem applies no stem.scale (pack it as NULL, or take the three-kernel route)", who,
+                 w->dtype == HMMR_BF16 ? "bf16" : "fp32");
+    return 0;
 }
 
 // Unit u on n images of H x H pixels.  have_raw / h1_ready: what the previous unit (the stem) left behind -- the raw trunk of this
@@ -317,6 +333,59 @@ static void set_residual(D& d, const void* x, int depth, int H, int stride) {
     d.res_img_stride = (int64_t)H * H * depth; d.res_row_stride = stride * H * depth; d.res_px_stride = stride * depth;
 }
 
+// ---- the stem of a pass, ALONE: route choice, the fused launch or the three launches, the three profile marks.  resnet_fwd_t and
+// hmmr_resnet50_stem both issue exactly this.  7x7/2 conv (+bias, no BN/ReLU) -> pool1 -> preact of block1/unit_1 -> pooled; h1 (may
+// be NULL: then nobody wants it) receives that unit's conv1 where stem_writes_conv1 says the fused kernel computes it.
+// Default: ONE fused kernel (csrc/stem.hip).  hmmr_debug_t.stem_route = 1 keeps the three-kernel route (re-pack, implicit GEMM, pool)
+// for A/B measurements.  In fp32-operand mode the fused kernel needs 104 KB of LDS (one workgroup per CU) and measures ~1 % slower
+// than the three-kernel route, which therefore stays the fp32 default.  f16x3 has its own fused kernel (stem_fused_split_kernel:
+// hi/lo planes, 32 output channels at a time).  xpad / stem: the re-packed image and the 112 x 112 conv map of the three-kernel route
+// (not touched by the fused one).
+template <typename T>
+static int stem_run(const hmmr_resnet_weights_t* w, const hmmr_debug_t* dbg, const float* images, int n_real, int n, T* pooled, T* h1,
+                    T* xpad, T* stem, hipStream_t s, Prof& pf) {
+    const int dt = w->dtype;
+    const hmmr_resnet_unit_t& U0 = w->unit[0];
+    if (!stem_unfused(w, dbg)) {
+        const bool stem_c1 = h1 && stem_writes_conv1(w, dbg);
+        if (hmmr_stem_fused(images, n_real, n, w->stem.w, w->stem.scale, w->stem.shift, U0.pre_scale, U0.pre_shift, pooled, dt, s,
+                            stem_c1 ? (dt == HMMR_F16X3 ? U0.conv1_frag : U0.conv1.w) : nullptr, U0.conv1.scale, U0.conv1.shift,
+                            stem_c1 ? h1 : nullptr))
+            return -2;
+        hmmr_count_launch(stem_c1 ? HMMR_COUNT_STEM_FUSED_CONV1 : HMMR_COUNT_STEM_FUSED);
+        if (prof_mark(pf)) return -2;
+        if (prof_mark(pf)) return -2;     // (keeps the profile slot numbering of the 3-kernel route)
+        if (prof_mark(pf)) return -2;
+    } else {
+        const long long npix = (long long)n * PADH * PADW;
+        const int grid = (int)((npix + 255) / 256 < 8192 ? (npix + 255) / 256 : 8192);
+        if constexpr (std::is_same<T, bsplit_t>::value)
+            hipLaunchKernelGGL(stem_repack_split_kernel, dim3(grid), dim3(256), 0, s, images, xpad, npix / 2, (long long)n_real);
+        else
+            hipLaunchKernelGGL(stem_repack_kernel<T>, dim3(grid), dim3(256), 0, s, images, xpad, npix, (long long)n_real);
+        HMMR_CHECK_HIP(hipGetLastError());
+        hmmr_count_launch(HMMR_COUNT_STEM_REPACK);
+        if (prof_mark(pf)) return -2;
+        hmmr_conv_desc_t d = {};
+        d.in = xpad; d.w = w->stem.w; d.scale = w->stem.scale; d.shift = w->stem.shift;
+        d.out = stem; d.in_dtype = d.out_dtype = dt;
+        d.n_img = n; d.hin = PADH; d.win = 2 * 111 + 1; d.cin = 32;
+        d.in_img_stride = (int64_t)PADH * PADW * 4; d.in_row_stride = PADW * 4; d.in_px_stride = 4;
+        d.kh = 8; d.kw = 1; d.sy = 2; d.sx = 2; d.py = 0; d.px = 0;
+        d.ho = 112; d.wo = 112; d.cout = 64; d.ldo = 64;
+        if (hmmr_conv_gemm(&d, s)) return -2;
+        hmmr_count_launch(HMMR_COUNT_STEM_GEMM);
+        if (prof_mark(pf)) return -2;
+        const long long nvec = (long long)n * 56 * 56 * 8;
+        const int g2 = (int)((nvec + 255) / 256 < 16384 ? (nvec + 255) / 256 : 16384);
+        hipLaunchKernelGGL(maxpool_bn_relu_kernel<T>, dim3(g2), dim3(256), 0, s, (const T*)stem, pooled, U0.pre_scale, U0.pre_shift, nvec);
+        HMMR_CHECK_HIP(hipGetLastError());
+        hmmr_count_launch(HMMR_COUNT_STEM_POOL);
+        if (prof_mark(pf)) return -2;
+    }
+    return 0;
+}
+
 template <typename T>
 static int resnet_fwd_t(const hmmr_resnet_weights_t* w, const float* images, int n_real, int n, float* phi,
                         char* ws, hipStream_t s, float* prof_ms) {
@@ -333,47 +402,8 @@ static int resnet_fwd_t(const hmmr_resnet_weights_t* w, const float* images, int
     Prof pf; pf.ms = prof_ms; pf.s = s; pf.slot = 0;
     if (prof_begin(pf)) return -2;
 
-    // ---- stem: 7x7/2 conv (+bias, no BN/ReLU) -> pool1 -> preact of block1/unit_1.
-    // Default: ONE fused kernel (csrc/stem.hip).  HMMR_STEM=unfused keeps the three-kernel route
-    // (re-pack, implicit GEMM, pool) for A/B measurements.
-    // In fp32-operand mode the fused kernel needs 104 KB of LDS (one workgroup per CU) and measures
-    // ~1 % slower than the three-kernel route, which therefore stays the fp32 default.  f16x3 has its own
-    // fused kernel (stem_fused_split_kernel: hi/lo planes, 32 output channels per workgroup).
-    const hmmr_debug_t* dbg = hmmr_debug_state();
-    const hmmr_resnet_unit_t& U0 = w->unit[0];
-    if (!stem_unfused(w, dbg)) {
-        const bool stem_c1 = stem_writes_conv1(w, dbg);
-        if (hmmr_stem_fused(images, n_real, n, w->stem.w, w->stem.scale, w->stem.shift, U0.pre_scale, U0.pre_shift, P[0], dt, s,
-                            stem_c1 ? (dt == HMMR_F16X3 ? U0.conv1_frag : U0.conv1.w) : nullptr, U0.conv1.scale, U0.conv1.shift,
-                            stem_c1 ? T1 : nullptr))
-            return -2;
-        if (prof_mark(pf)) return -2;
-        if (prof_mark(pf)) return -2;     // (keeps the profile slot numbering of the 3-kernel route)
-        if (prof_mark(pf)) return -2;
-    } else {
-        const long long npix = (long long)n * PADH * PADW;
-        const int grid = (int)((npix + 255) / 256 < 8192 ? (npix + 255) / 256 : 8192);
-        if constexpr (std::is_same<T, bsplit_t>::value)
-            hipLaunchKernelGGL(stem_repack_split_kernel, dim3(grid), dim3(256), 0, s, images, xpad, npix / 2, (long long)n_real);
-        else
-            hipLaunchKernelGGL(stem_repack_kernel<T>, dim3(grid), dim3(256), 0, s, images, xpad, npix, (long long)n_real);
-        HMMR_CHECK_HIP(hipGetLastError());
-        if (prof_mark(pf)) return -2;
-        hmmr_conv_desc_t d = {};
-        d.in = xpad; d.w = w->stem.w; d.scale = w->stem.scale; d.shift = w->stem.shift;
-        d.out = stem; d.in_dtype = d.out_dtype = dt;
-        d.n_img = n; d.hin = PADH; d.win = 2 * 111 + 1; d.cin = 32;
-        d.in_img_stride = (int64_t)PADH * PADW * 4; d.in_row_stride = PADW * 4; d.in_px_stride = 4;
-        d.kh = 8; d.kw = 1; d.sy = 2; d.sx = 2; d.py = 0; d.px = 0;
-        d.ho = 112; d.wo = 112; d.cout = 64; d.ldo = 64;
-        if (hmmr_conv_gemm(&d, s)) return -2;
-        if (prof_mark(pf)) return -2;
-        const long long nvec = (long long)n * 56 * 56 * 8;
-        const int g2 = (int)((nvec + 255) / 256 < 16384 ? (nvec + 255) / 256 : 16384);
-        hipLaunchKernelGGL(maxpool_bn_relu_kernel<T>, dim3(g2), dim3(256), 0, s, (const T*)stem, P[0], U0.pre_scale, U0.pre_shift, nvec);
-        HMMR_CHECK_HIP(hipGetLastError());
-        if (prof_mark(pf)) return -2;
-    }
+    // ---- stem: 7x7/2 conv (+bias, no BN/ReLU) -> pool1 -> preact of block1/unit_1 (-> P[0]) [+ that unit's conv1 -> T1]
+    if (stem_run<T>(w, hmmr_debug_state(), images, n_real, n, P[0], T1, xpad, stem, s, pf)) return -2;
 
     // ---- units.  X[cur]: the raw trunk, P[pcur]: its pre-activated form (each where the plan has it written), T1 / T2: conv1's and
     // conv2's outputs.  Every layer owns one profile slot per pass -- [shortcut] conv1 conv2 conv3 -- whether or not the plan gives it a
@@ -473,9 +503,41 @@ extern "C" int hmmr_resnet50_fwd(const hmmr_resnet_weights_t* w, const float* im
                  "hmmr_resnet50_fwd: workspace too small (%zu < %zu)", ws_bytes,
                  hmmr_resnet50_workspace_bytes(nt, w->dtype));
     HMMR_REQUIRE(w->unit[0].c_in == 64 && w->unit[15].depth == 2048, "hmmr_resnet50_fwd: bad unit table");
+    HMMR_REQUIRE(w->dtype == HMMR_BF16 || w->dtype == HMMR_F32 || w->dtype == HMMR_F16X3, "hmmr_resnet50_fwd: bad dtype %d", w->dtype);
+    if (stem_check(w, images, hmmr_debug_state(), "hmmr_resnet50_fwd")) return -1;
     if (w->dtype == HMMR_BF16) return resnet_fwd_t<bf16_t>(w, images, n, nt, phi, (char*)ws, (hipStream_t)stream, prof_ms);
     if (w->dtype == HMMR_F32) return resnet_fwd_t<float>(w, images, n, nt, phi, (char*)ws, (hipStream_t)stream, prof_ms);
-    if (w->dtype == HMMR_F16X3) return resnet_fwd_t<bsplit_t>(w, images, n, nt, phi, (char*)ws, (hipStream_t)stream, prof_ms);
-    hmmr_set_error("hmmr_resnet50_fwd: bad dtype %d", w->dtype);
-    return -1;
+    return resnet_fwd_t<bsplit_t>(w, images, n, nt, phi, (char*)ws, (hipStream_t)stream, prof_ms);
+}
+
+// ---- the stem alone (include/hmmr_hip.h): what hmmr_resnet50_fwd launches first, into caller-owned tensors
+extern "C" size_t hmmr_resnet50_stem_workspace_bytes(const hmmr_resnet_weights_t* w, int n_total) {
+    if (!w || n_total <= 0 || (w->dtype != HMMR_BF16 && w->dtype != HMMR_F32 && w->dtype != HMMR_F16X3)) return 0;
+    return stem_unfused(w, hmmr_debug_state()) ? resnet_layout(n_total, w->dtype).x[0] : 0;      // xpad + the conv map
+}
+
+extern "C" int hmmr_resnet50_stem(const hmmr_resnet_weights_t* w, const float* images, int n, int n_zero, void* pooled, void* h1,
+                                  int* h1_written, void* ws, size_t ws_bytes, void* stream) {
+    if (h1_written) *h1_written = 0;
+    HMMR_REQUIRE(w && pooled && (images || n == 0), "hmmr_resnet50_stem: null argument");
+    HMMR_REQUIRE(n >= 0 && n_zero >= 0 && n + n_zero > 0, "hmmr_resnet50_stem: need at least one image");
+    HMMR_REQUIRE(w->dtype == HMMR_BF16 || w->dtype == HMMR_F32 || w->dtype == HMMR_F16X3, "hmmr_resnet50_stem: bad dtype %d", w->dtype);
+    const int nt = n + n_zero;
+    const size_t need = hmmr_resnet50_stem_workspace_bytes(w, nt);
+    HMMR_REQUIRE(ws_bytes >= need && (ws || !need), "hmmr_resnet50_stem: workspace too small (%zu < %zu)", ws ? ws_bytes : (size_t)0, need);
+    const hmmr_debug_t* dbg = hmmr_debug_state();
+    if (stem_check(w, images, dbg, "hmmr_resnet50_stem")) return -1;
+    const ResnetBufs L = resnet_layout(nt, w->dtype);
+    char* base = need ? (char*)ws : nullptr;           // (the fused route touches neither buffer)
+    Prof pf; pf.ms = nullptr; pf.s = (hipStream_t)stream; pf.slot = 0;
+    int rc;
+    if (w->dtype == HMMR_BF16)
+        rc = stem_run<bf16_t>(w, dbg, images, n, nt, (bf16_t*)pooled, (bf16_t*)h1, base ? (bf16_t*)(base + L.xpad) : nullptr, base ? (bf16_t*)(base + L.stem) : nullptr, pf.s, pf);
+    else if (w->dtype == HMMR_F32)
+        rc = stem_run<float>(w, dbg, images, n, nt, (float*)pooled, (float*)h1, base ? (float*)(base + L.xpad) : nullptr, base ? (float*)(base + L.stem) : nullptr, pf.s, pf);
+    else
+        rc = stem_run<bsplit_t>(w, dbg, images, n, nt, (bsplit_t*)pooled, (bsplit_t*)h1, base ? (bsplit_t*)(base + L.xpad) : nullptr, base ? (bsplit_t*)(base + L.stem) : nullptr, pf.s, pf);
+    if (rc) return rc;
+    if (h1_written) *h1_written = (h1 && stem_writes_conv1(w, dbg)) ? 1 : 0;
+    return 0;
 }

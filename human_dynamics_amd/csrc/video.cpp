@@ -128,6 +128,7 @@ extern "C" int hmmr_predict_video(const hmmr_model_t* model, const float* images
     if (n == 0) return 0;
     VIDEO_REQUIRE(images && rec && ws, "hmmr_predict_video: null images, rec or ws");
     VIDEO_REQUIRE(((uintptr_t)ws & 255u) == 0, "hmmr_predict_video: ws must be 256-byte aligned");
+    VIDEO_REQUIRE(((uintptr_t)images & 15u) == 0, "hmmr_predict_video: images must be 16-byte aligned (hmmr_resnet50_fwd reads them as aligned groups of 4 floats)");
     Carve c;
     if (carve(model, p, &c)) return -1;
     VIDEO_REQUIRE(ws_bytes >= c.total, "hmmr_predict_video: workspace too small (%zu < %zu)", ws_bytes, c.total);

@@ -929,3 +929,79 @@ def unit_pair(h2, W3, bias3, pre, W1, bn1, **kw):
     c.run()
     torch.cuda.synchronize(c.dev)
     return c.trunk, c.h1
+
+
+STEM_SENTINEL_BYTE = 0x5a           # every byte of a StemCall's outputs before the launch (bf16 0x5a5a and fp32 0x5a5a5a5a are ~1.5e16)
+STEM_GUARD_ROWS = 4                 # 64-channel rows of sentinel behind each output; as many image ROWS of NaN behind the input
+
+
+def pack_stem(weights, dtype, device="cuda:0"):
+    """(hmmr_resnet_weights_t, the DeviceStore that owns its tensors): packing.pack_resnet of a checkpoint-named dict in the shipped
+    configuration -- the table a StemCall reads.  Host work; a caller with several calls on one weight set packs once."""
+    store = packing.DeviceStore(torch.device(device))
+    return packing.pack_resnet(weights, _dt(dtype), store), store
+
+
+class StemCall(object):
+    """Test/utility entry for the ResNet stem ALONE (hmmr_resnet50_stem: the launches hmmr_resnet50_fwd starts with; csrc/stem.hip or the
+    three-kernel route of csrc/resnet.hip).  images [n,224,224,3] float (host or device; n may be 0), weights: a checkpoint-named dict
+    (packed here with packing.pack_resnet) or packed = pack_stem(...)'s result; route / no_conv1: hmmr_debug_t.stem_route /
+    stem_no_conv1 for this call only (the other switches stay as they are).
+    The input buffer holds exactly the n images followed by STEM_GUARD_ROWS image rows of NaN; both outputs start as STEM_SENTINEL_BYTE
+    in every byte, valid rows included, and are followed by STEM_GUARD_ROWS rows of it.  .pooled / .h1: [(n + n_zero) 56 56 +
+    STEM_GUARD_ROWS, 64] in the mode's storage type (bf16, fp32, int32 split words); .h1_written after run()."""
+
+    def __init__(self, images, weights, dtype, n_zero=0, route=0, no_conv1=0, device="cuda:0", packed=None):
+        self.lib = L.load()
+        dev = self.dev = torch.device(device)
+        self.dtype = _dt(dtype)
+        self.rw, self.store = packed if packed is not None else pack_stem(weights, self.dtype, dev)
+        images = torch.as_tensor(np.asarray(images) if not isinstance(images, torch.Tensor) else images, dtype=torch.float32)
+        n = self.n = int(images.shape[0])
+        assert n == 0 or tuple(images.shape[1:]) == (224, 224, 3), images.shape
+        self.n_zero, self.route, self.no_conv1 = int(n_zero), int(route), int(no_conv1)
+        per = 224 * 224 * 3
+        self.images = torch.full((n * per + STEM_GUARD_ROWS * 224 * 3,), float("nan"), dtype=torch.float32, device=dev)
+        if n:
+            self.images[:n * per] = images.reshape(-1).to(dev)
+        td = {L.HMMR_F32: torch.float32, L.HMMR_BF16: torch.bfloat16, L.HMMR_F16X3: torch.int32}[self.dtype]
+        self.rows = (n + self.n_zero) * 56 * 56
+        mk = lambda: torch.full(((self.rows + STEM_GUARD_ROWS) * 64 * td.itemsize,), STEM_SENTINEL_BYTE, dtype=torch.uint8,
+                                device=dev).view(td).reshape(self.rows + STEM_GUARD_ROWS, 64)
+        self.pooled, self.h1 = mk(), mk()
+        self.h1_written = None
+        # what run() passes: a test may edit these
+        self.args = dict(images=self.images.data_ptr() if n else None, n=n, n_zero=self.n_zero, pooled=self.pooled.data_ptr(),
+                         h1=self.h1.data_ptr(), ws="query", ws_bytes="query")
+
+    def run(self):
+        """launch on the current stream under this call's two debug switches (no synchronisation)"""
+        old, d = L.Debug(), L.Debug()
+        self.lib.hmmr_get_debug(C.byref(old))
+        self.lib.hmmr_get_debug(C.byref(d))
+        d.stem_route, d.stem_no_conv1 = self.route, self.no_conv1
+        try:
+            self.lib.hmmr_set_debug(C.byref(d))
+            a = dict(self.args)
+            if a["ws_bytes"] == "query":
+                a["ws_bytes"] = self.lib.hmmr_resnet50_stem_workspace_bytes(C.byref(self.rw), a["n"] + a["n_zero"])
+            if a["ws"] == "query":
+                self.ws = torch.empty(max(int(a["ws_bytes"]), 0), dtype=torch.uint8, device=self.dev) if a["ws_bytes"] else None
+                a["ws"] = L.ptr(self.ws)
+            written = C.c_int(-1)
+            L.check(self.lib.hmmr_resnet50_stem(C.byref(self.rw), a["images"], a["n"], a["n_zero"], a["pooled"], a["h1"], C.byref(written),
+                                                a["ws"], a["ws_bytes"], torch.cuda.current_stream(self.dev).cuda_stream),
+                    "hmmr_resnet50_stem")
+            self.h1_written = bool(written.value)
+        finally:
+            self.lib.hmmr_set_debug(C.byref(old))
+
+
+def stem(images, weights, dtype, n_zero=0, route=0, no_conv1=0, device="cuda:0", packed=None):
+    """StemCall(...) run once: (pooled, h1 or None) [n + n_zero, 56, 56, 64] as raw storage tensors (packing.from_split decodes f16x3);
+    h1 is None where the schedule leaves block1/unit_1's conv1 to its own launch.  Nothing is cached between calls."""
+    c = StemCall(images, weights, dtype, n_zero=n_zero, route=route, no_conv1=no_conv1, device=device, packed=packed)
+    c.run()
+    torch.cuda.synchronize(c.dev)
+    nt = c.n + c.n_zero
+    return c.pooled[:c.rows].reshape(nt, 56, 56, 64), (c.h1[:c.rows].reshape(nt, 56, 56, 64) if c.h1_written else None)

@@ -97,6 +97,16 @@ typedef struct {
     unsigned long long conv1x1_stream;  /* csrc/conv1x1_stream.hip (ABI 17) */
 } hmmr_launch_counts_t;
 void hmmr_launch_counts(hmmr_launch_counts_t* out, int clear);
+/* ... and of the stem's launches, wherever they were issued (hmmr_resnet50_fwd or hmmr_resnet50_stem); a struct of its own, so
+ * hmmr_launch_counts_t keeps its size.  One pass adds 1 to `fused` OR `fused_conv1`, or 1 to each of `repack`, `gemm`, `pool`. */
+typedef struct {
+    unsigned long long fused;           /* csrc/stem.hip, pooled tensor only */
+    unsigned long long fused_conv1;     /* csrc/stem.hip with block1/unit_1's conv1 inside the launch */
+    unsigned long long repack;          /* the three-kernel route: stem_repack*, */
+    unsigned long long gemm;            /* ... its hmmr_conv_gemm, */
+    unsigned long long pool;            /* ... maxpool_bn_relu_kernel */
+} hmmr_stem_counts_t;
+void hmmr_stem_launch_counts(hmmr_stem_counts_t* out, int clear);
 
 /* ------------------------------------------------------------------------- *
  * Generic implicit-GEMM convolution / fully-connected building block.
@@ -353,8 +363,25 @@ size_t hmmr_resnet50_workspace_bytes(int n, int dtype);
 /* n_zero: that many all-zero images are appended after the n real ones (the padding frames of
  * predict_all_images, tester.py:285-289, are zero IMAGES that still go through the encoder);
  * phi has n + n_zero rows, the workspace must be sized for n + n_zero. */
+/* images must be 16-byte aligned (every image then is: 224 x 224 x 3 floats are a multiple of 16 bytes): the fused stem kernels read
+ * them as aligned groups of 4 floats.  A pointer that is not is refused before anything is queued, on either stem route. */
 int hmmr_resnet50_fwd(const hmmr_resnet_weights_t* w, const float* images, int n, int n_zero,
                       float* phi, void* ws, size_t ws_bytes, void* stream, float* prof_ms);
+
+/* The stem of that pass ALONE: exactly the launches hmmr_resnet50_fwd starts with (one function issues both), into tensors the caller
+ * owns -- 7x7/2 conv + bias, the 3x3/2 TF-SAME max pool, the pre-activation BN + ReLU of block1/unit_1 -> pooled [n + n_zero][56][56][64]
+ * in the storage type of w->dtype, and, where the schedule has the fused kernel compute it (bf16; f16x3 with unit[0].conv1_frag; not
+ * with hmmr_debug_t.stem_no_conv1 or on the three-kernel route), that unit's conv1 + BN + ReLU -> h1 of the same shape.  h1 may be
+ * NULL (then it is not computed); *h1_written (may be NULL) says whether h1 was written.  hmmr_debug_t.stem_route / stem_no_conv1 are
+ * honoured as in the full pass.  The workspace (the re-packed image and the 112 x 112 conv map) is needed by the three-kernel route only:
+ * the query answers 0 for the fused route under the CURRENT debug switches, and ws may then be NULL.
+ * Refused before anything is queued: a null argument (images may be NULL only when n == 0), n < 0, n_zero < 0, n + n_zero == 0, a bad
+ * dtype, a short workspace, images not 16-byte aligned, and -- on the fused route in bf16 / fp32 mode -- a non-NULL stem.scale: that
+ * kernel applies none, the three-kernel route does, so the two would disagree (hmmr_resnet50_fwd refuses the last two as well).
+ * For tests and measurements of the stem (tests/test_gpu_stem.py); a product pass calls hmmr_resnet50_fwd. */
+size_t hmmr_resnet50_stem_workspace_bytes(const hmmr_resnet_weights_t* w, int n_total);
+int hmmr_resnet50_stem(const hmmr_resnet_weights_t* w, const float* images, int n, int n_zero, void* pooled, void* h1,
+                       int* h1_written, void* ws, size_t ws_bytes, void* stream);
 
 /* What hmmr_resnet50_fwd launches for one unit: decided for all 16 units, from the unit table, the frame count and hmmr_debug_t,
  * BEFORE the first launch (an inconsistent table is refused with the unit named and nothing queued), then issued in order.
@@ -965,7 +992,8 @@ typedef struct {
  * frame (hmmr_record_layout, or any layout hmmr_smpl_fwd_records accepts: field_offsets is a HOST array
  * [ief->num_regressors][7]).  Everything is queued on `stream`; nothing is allocated or synchronised.  Model pointers, the
  * plan, every unit table, ws_bytes and ld_rec against the end of the last field are checked BEFORE the first launch: a
- * refused call (-1) queues nothing.  n = 0: returns 0, queues nothing.
+ * refused call (-1) queues nothing.  n = 0: returns 0, queues nothing.  images must be 16-byte aligned, as for hmmr_resnet50_fwd
+ * (every pass then starts on an aligned image); a pointer that is not is among the refusals.
  *   1. ResNet passes of at most max_frames frames (hmmr_resnet50_fwd, one launch sequence each) into phi [n + 1][2048]
  *      inside `ws`; the last pass appends the zero image (n_zero = 1), whose feature fills every padding slot;
  *   2. tail passes of at most max_windows windows: hmmr_gather_windows, hmmr_temporal_fwd (or hmmr_hallucinator_fwd over

@@ -204,3 +204,116 @@ def test_integration_doc_stub_matches_the_struct():
     doc_fields = re.findall(r"\('(\w+)',\s*C\.(\w+)\)", block)
     lib_fields = [(n, "c_int" if t is C.c_int else "c_void_p") for n, t in _lib.SmplConsts._fields_]
     assert doc_fields == lib_fields
+
+
+def _stem_table(dtype, conv1_frag=True):
+    """a table whose stem and block1/unit_1 hold dummy (never dereferenced) pointers: every check runs before anything is queued"""
+    rw = _lib.ResnetWeights()
+    rw.dtype = dtype
+    rw.stem.w, rw.stem.shift = 0x1000, 0x2000
+    if dtype == _lib.HMMR_F16X3:
+        rw.stem.scale = 0x3000                       # the pack-time row scale of the split filters
+    u = rw.unit[0]
+    u.pre_scale, u.pre_shift = 0x4000, 0x5000
+    u.conv1.w, u.conv1.scale, u.conv1.shift = 0x6000, 0x7000, 0x8000
+    if dtype == _lib.HMMR_F16X3 and conv1_frag:
+        u.conv1_frag = 0x9000
+    u.c_in, u.base, u.depth, u.stride = 64, 64, 256, 1
+    rw.unit[15].depth = 2048
+    return rw
+
+
+class _stem_switches(object):
+    """hmmr_debug_t.stem_route / stem_no_conv1 for the block; every switch is put back as it was found"""
+
+    def __init__(self, lib, route, no_conv1=0):
+        self.lib, self.route, self.no_conv1 = lib, route, no_conv1
+
+    def __enter__(self):
+        import ctypes as C
+        self.old, d = _lib.Debug(), _lib.Debug()
+        self.lib.hmmr_get_debug(C.byref(self.old))
+        self.lib.hmmr_get_debug(C.byref(d))
+        d.stem_route, d.stem_no_conv1 = self.route, self.no_conv1
+        self.lib.hmmr_set_debug(C.byref(d))
+
+    def __exit__(self, *exc):
+        import ctypes as C
+        self.lib.hmmr_set_debug(C.byref(self.old))
+        return False
+
+
+def test_stem_entry_refuses_before_anything_is_queued():
+    """hmmr_resnet50_stem: every refusal of include/hmmr_hip.h, with dummy pointers and no device -- a call that got past its checks would
+    have to launch.  hmmr_resnet50_fwd refuses a misaligned image pointer and a scaled bf16 / fp32 fused stem as well."""
+    import ctypes as C
+    lib = _lib.load()
+    IMG, OUT, H1, WS = 0x10000, 0x20000, 0x30000, 0x40000
+    BIG = 1 << 40
+
+    def stem(rw, images=IMG, n=2, n_zero=1, pooled=OUT, h1=H1, ws=WS, ws_bytes=BIG, route=0, no_conv1=0):
+        flag = C.c_int(7)
+        with _stem_switches(lib, route, no_conv1):
+            rc = lib.hmmr_resnet50_stem(C.byref(rw) if rw is not None else None, images, n, n_zero, pooled, h1, C.byref(flag), ws, ws_bytes, None)
+        return rc, flag.value, lib.hmmr_last_error()
+
+    def refused(res, *words):
+        rc, flag, msg = res
+        assert rc == -1 and flag == 0 and b"hmmr_resnet50_stem" in msg, res
+        for w in words:
+            assert w in msg, (w, msg)
+
+    for dt in (_lib.HMMR_F32, _lib.HMMR_BF16, _lib.HMMR_F16X3):
+        rw = _stem_table(dt)
+        for route in (1, 2):
+            refused(stem(None, route=route), b"null argument")
+            refused(stem(rw, pooled=None, route=route), b"null argument")
+            refused(stem(rw, images=None, route=route), b"null argument")            # n = 2 images, no pointer
+            refused(stem(rw, n=-1, route=route), b"at least one image")
+            refused(stem(rw, n_zero=-1, route=route), b"at least one image")
+            refused(stem(rw, n=0, n_zero=0, route=route), b"at least one image")
+            refused(stem(rw, n=0, n_zero=0, images=None, route=route), b"at least one image")
+            for off in (4, 8, 12, 1):
+                refused(stem(rw, images=IMG + off, route=route), b"16-byte aligned")
+        # the three-kernel route needs the re-packed image and the conv map; the fused one no workspace at all
+        with _stem_switches(lib, 1):
+            need = lib.hmmr_resnet50_stem_workspace_bytes(C.byref(rw), 3)
+        with _stem_switches(lib, 2):
+            assert lib.hmmr_resnet50_stem_workspace_bytes(C.byref(rw), 3) == 0
+        e = 2 if dt == _lib.HMMR_BF16 else 4
+        assert need >= 3 * (230 * 232 * 4 + 112 * 112 * 64) * e and need < lib.hmmr_resnet50_workspace_bytes(3, dt)
+        assert lib.hmmr_resnet50_stem_workspace_bytes(C.byref(rw), 0) == 0 and lib.hmmr_resnet50_stem_workspace_bytes(None, 3) == 0
+        refused(stem(rw, ws_bytes=need - 1, route=1), b"workspace too small")
+        refused(stem(rw, ws=None, route=1), b"workspace too small")
+        for part in ("w", "shift"):
+            bad = _stem_table(dt)
+            setattr(bad.stem, part, None)
+            refused(stem(bad, route=1), b"null argument")
+            refused(stem(bad, route=2), b"null argument")
+        bad = _stem_table(dt)
+        bad.unit[0].pre_shift = None
+        refused(stem(bad, route=2), b"null argument")
+    for bad_dt in (3, -1, 17):
+        refused(stem(_stem_table(bad_dt)), b"bad dtype")
+    # a scaled bf16 / fp32 stem on the fused route (default route for bf16, forced for fp32); the three-kernel route would apply it
+    for dt, routes, word in ((_lib.HMMR_BF16, (0, 2), b"bf16"), (_lib.HMMR_F32, (2,), b"fp32")):
+        rw = _stem_table(dt)
+        rw.stem.scale = 0x3000
+        for route in routes:
+            refused(stem(rw, route=route), b"stem.scale", word)
+
+    # hmmr_resnet50_fwd: the same two refusals, before its first launch
+    def fwd(rw, images=IMG, route=0):
+        with _stem_switches(lib, route):
+            return lib.hmmr_resnet50_fwd(C.byref(rw), images, 2, 1, OUT, WS, BIG, None, None), lib.hmmr_last_error()
+
+    for dt in (_lib.HMMR_F32, _lib.HMMR_BF16, _lib.HMMR_F16X3):
+        for route in (0, 1, 2):
+            rc, msg = fwd(_stem_table(dt), images=IMG + 4, route=route)
+            assert rc == -1 and b"hmmr_resnet50_fwd" in msg and b"16-byte aligned" in msg, (rc, msg)
+    rw = _stem_table(_lib.HMMR_BF16)
+    rw.stem.scale = 0x3000
+    rc, msg = fwd(rw)
+    assert rc == -1 and b"hmmr_resnet50_fwd" in msg and b"stem.scale" in msg, (rc, msg)
+    rc, msg = fwd(_stem_table(5))
+    assert rc == -1 and b"bad dtype" in msg, (rc, msg)

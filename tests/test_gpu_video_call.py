@@ -203,8 +203,8 @@ def test_refused_calls_queue_nothing(testers, frames24, gpu_device):
     nbytes = lib.hmmr_predict_video_workspace_bytes(C.byref(model), N, 1024, 128)
     ws = torch.empty(nbytes, dtype=torch.uint8, device=gpu_device)
 
-    def call(model=model, ws_bytes=nbytes, ld_rec=rec_len):
-        return lib.hmmr_predict_video(C.byref(model), frames.data_ptr(), N, rec.data_ptr(), ld_rec, offs, 1024, 128, ws.data_ptr(), ws_bytes,
+    def call(model=model, ws_bytes=nbytes, ld_rec=rec_len, images=None):
+        return lib.hmmr_predict_video(C.byref(model), images or frames.data_ptr(), N, rec.data_ptr(), ld_rec, offs, 1024, 128, ws.data_ptr(), ws_bytes,
                                       _stream(gpu_device))
 
     def refused(rc, word):
@@ -223,6 +223,7 @@ def test_refused_calls_queue_nothing(testers, frames24, gpu_device):
     even = t.native_model()
     even.fov = 12
     refused(call(model=even), b"odd")
+    refused(call(images=frames.data_ptr() + 4), b"images must be 16-byte aligned")      # -1 from the call's own checks, not -2 from its first pass
     # the same arguments, accepted: the sentinel is gone and the records are the Tester's
     assert call() == 0
     torch.cuda.synchronize(gpu_device)
