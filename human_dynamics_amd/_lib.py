@@ -162,6 +162,15 @@ class VideoPlan(C.Structure):
     _fields_ = [(k, C.c_int) for k in ("n", "T", "fov", "margin", "g", "n_windows", "max_frames", "max_windows", "resnet_passes", "tail_passes")]
 
 
+class TracksPlan(C.Structure):
+    """hmmr_tracks_plan_t: the plan of a call over several tracks laid end to end (csrc/video_plan.cpp; host only).  Track k holds
+    frames [off[k], off[k + 1]) and ceil(n_k / g) windows; windows are numbered globally, track after track; slot t of local window lw
+    holds frame lw g + t - margin of ITS track or the zero image, and its slots margin .. margin + g - 1 are the track's output rows
+    off[k] + lw g .. (include/hmmr_hip.h)"""
+    _fields_ = [(k, C.c_int) for k in ("n_tracks", "T", "fov", "margin", "g", "n_frames", "n_windows", "max_frames", "max_windows",
+                                       "resnet_passes", "tail_passes")]
+
+
 class Model(C.Structure):
     """hmmr_model_t: the packed stages of one model, as hmmr_predict_video reads them"""
     _fields_ = [("resnet", C.POINTER(ResnetWeights)), ("temporal", C.POINTER(TemporalWeights)), ("hallucinator", C.POINTER(HallucinatorWeights)),
@@ -305,6 +314,17 @@ SIGNATURES = {
     "hmmr_predict_video_workspace_bytes": (C.c_size_t, [C.POINTER(Model), C.c_int, C.c_int, C.c_int]),
     "hmmr_predict_video": (C.c_int, [C.POINTER(Model), _fp, C.c_int, _fp, C.c_int64, C.POINTER(C.c_int32), C.c_int, C.c_int,
                                      _vp, C.c_size_t, _vp]),
+    "hmmr_tracks_plan": (C.c_int, [C.POINTER(C.c_int32), C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(TracksPlan)]),
+    "hmmr_tracks_window_owner": (C.c_int, [C.POINTER(C.c_int32), C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int)]),
+    "hmmr_tracks_window_rows": (C.c_int, [C.POINTER(C.c_int32), C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int)]),
+    "hmmr_tracks_tail_pass": (C.c_int, [C.POINTER(C.c_int32), C.c_int, C.POINTER(TracksPlan), C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int),
+                                        C.POINTER(C.c_int), C.POINTER(C.c_int)]),
+    "hmmr_gather_windows_tracks": (C.c_int, [_fp, _fp, C.POINTER(C.c_int32), C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _fp, _vp]),
+    "hmmr_keep_rows_tracks": (C.c_int, [_fp, C.POINTER(C.c_int32), C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _fp, C.c_int64,
+                                        _vp]),
+    "hmmr_predict_tracks_workspace_bytes": (C.c_size_t, [C.POINTER(Model), C.POINTER(C.c_int32), C.c_int, C.c_int, C.c_int]),
+    "hmmr_predict_tracks": (C.c_int, [C.POINTER(Model), _fp, C.POINTER(C.c_int32), C.c_int, _fp, C.c_int64, C.POINTER(C.c_int32), C.c_int, C.c_int,
+                                      _vp, C.c_size_t, _vp]),
 }
 
 _lib = None

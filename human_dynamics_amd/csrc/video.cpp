@@ -1,4 +1,4 @@
-// hmmr_predict_video (include/hmmr_hip.h): Tester.predict_all_images (src/evaluation/tester.py:260-312) as ONE call of the C ABI -- the
+// hmmr_predict_video and hmmr_predict_tracks (include/hmmr_hip.h): Tester.predict_all_images (src/evaluation/tester.py:260-312) as ONE call of the C ABI -- the
 // frames of a video on the device in, the packed per-frame records on the device out, no Python and no torch in between.  The call
 // only sequences the stage entry points on the caller's stream: ResNet passes into phi, then per tail pass gather -> f_movie (or the
 // hallucinator) -> keep -> IEF -> SMPL records.  It owns no kernel and makes no HIP call itself; every check that a stage would make
@@ -39,7 +39,6 @@ inline TailPass tail_pass(const hmmr_video_plan_t& p, int i) {
     t.keep = (int)((o1 < p.n ? o1 : (long long)p.n) - o0);
     return t;
 }
-inline int resnet_pass_frames(const hmmr_video_plan_t& p, int i) { return imin(p.max_frames, p.n - i * p.max_frames); }
 
 // model pointers and everything the stages would refuse that does not depend on the frame count
 int check_model(const hmmr_model_t* m, const char* who) {
@@ -64,35 +63,99 @@ int check_model(const hmmr_model_t* m, const char* who) {
     return 0;
 }
 
-// n > 0.  The sizes of the first and of the last pass bound every pass between them (all but the last are full).
-int carve(const hmmr_model_t* m, const hmmr_video_plan_t& p, Carve* out) {
+// what the tail's buffers must hold: the largest window count, the largest kept-row count and the largest workspace of every stage
+// over the passes added (the stages' queries are asked per pass size, never assumed monotone)
+struct TailNeeds { int mw, mk; size_t movie_bytes, ief_bytes, smpl_bytes; };
+void tail_needs_add(const hmmr_model_t* m, int T, const TailPass& t, TailNeeds* need) {
+    auto max2 = [](size_t a, size_t b) { return a > b ? a : b; };
+    const int R = m->ief->num_regressors;
+    const size_t movie = m->temporal ? hmmr_temporal_workspace_bytes(t.nw, T, m->temporal->dtype)
+                                     : hmmr_hallucinator_workspace_bytes(t.nw * T, m->hallucinator->dtype);
+    const size_t ief = hmmr_ief_workspace_bytes(t.keep, R, m->ief->dtype), smpl = hmmr_smpl_workspace_bytes(R * t.keep);
+    need->mw = t.nw > need->mw ? t.nw : need->mw;
+    need->mk = t.keep > need->mk ? t.keep : need->mk;
+    need->movie_bytes = max2(need->movie_bytes, movie);
+    need->ief_bytes = max2(need->ief_bytes, ief);
+    need->smpl_bytes = max2(need->smpl_bytes, smpl);
+}
+
+// n > 0 frames in all, at most resnet_frames of them (and the zero image) in one ResNet pass
+int carve(const hmmr_model_t* m, const char* who, int n, int resnet_frames, int T, const TailNeeds& need, Carve* out) {
     Carve c = {};
     const int R = m->ief->num_regressors;
     size_t off = 0;
-    c.phi = off; off += align_up((size_t)(p.n + 1) * C * 4);
+    c.phi = off; off += align_up((size_t)(n + 1) * C * 4);
     c.region = off;
-    c.resnet_bytes = hmmr_resnet50_workspace_bytes(imin(p.n, p.max_frames) + 1, m->resnet->dtype);
-    VIDEO_REQUIRE(c.resnet_bytes > 0, "hmmr_predict_video: no ResNet workspace for this dtype");
-    const int mw = imin(p.n_windows, p.max_windows);
-    const TailPass first = tail_pass(p, 0), last = tail_pass(p, p.tail_passes - 1);
-    const int mk = first.keep > last.keep ? first.keep : last.keep;
+    c.resnet_bytes = hmmr_resnet50_workspace_bytes(resnet_frames + 1, m->resnet->dtype);
+    VIDEO_REQUIRE(c.resnet_bytes > 0, "%s: no ResNet workspace for this dtype", who);
     size_t t = 0;
-    c.windows = t; t += align_up((size_t)mw * p.T * C * 4);
-    c.strips = t;  t += align_up((size_t)mw * p.T * C * 4);
-    c.kept = t;    t += align_up((size_t)mk * C * 4);
-    c.omegas = t;  t += align_up((size_t)R * mk * 85 * 4);
-    auto movie = [&](int nw) { return m->temporal ? hmmr_temporal_workspace_bytes(nw, p.T, m->temporal->dtype)
-                                                  : hmmr_hallucinator_workspace_bytes(nw * p.T, m->hallucinator->dtype); };
-    auto max2 = [](size_t a, size_t b) { return a > b ? a : b; };
-    c.movie_bytes = max2(movie(first.nw), movie(last.nw));
-    c.ief_bytes = max2(hmmr_ief_workspace_bytes(first.keep, R, m->ief->dtype), hmmr_ief_workspace_bytes(last.keep, R, m->ief->dtype));
-    c.smpl_bytes = max2(hmmr_smpl_workspace_bytes(R * first.keep), hmmr_smpl_workspace_bytes(R * last.keep));
-    VIDEO_REQUIRE(c.movie_bytes && c.ief_bytes && c.smpl_bytes, "hmmr_predict_video: a stage reports no workspace for this model");
+    c.windows = t; t += align_up((size_t)need.mw * T * C * 4);
+    c.strips = t;  t += align_up((size_t)need.mw * T * C * 4);
+    c.kept = t;    t += align_up((size_t)need.mk * C * 4);
+    c.omegas = t;  t += align_up((size_t)R * need.mk * 85 * 4);
+    c.movie_bytes = need.movie_bytes; c.ief_bytes = need.ief_bytes; c.smpl_bytes = need.smpl_bytes;
+    VIDEO_REQUIRE(c.movie_bytes && c.ief_bytes && c.smpl_bytes, "%s: a stage reports no workspace for this model", who);
     c.movie_ws = t; t += align_up(c.movie_bytes);
     c.ief_ws = t;   t += align_up(c.ief_bytes);
     c.smpl_ws = t;  t += align_up(c.smpl_bytes);
     c.total = c.region + (t > align_up(c.resnet_bytes) ? t : align_up(c.resnet_bytes));
     *out = c;
+    return 0;
+}
+
+// one video, n > 0.  The sizes of the first and of the last pass bound every pass between them (all but the last are full).
+int carve_video(const hmmr_model_t* m, const hmmr_video_plan_t& p, Carve* out) {
+    TailNeeds need = {};
+    tail_needs_add(m, p.T, tail_pass(p, 0), &need);
+    tail_needs_add(m, p.T, tail_pass(p, p.tail_passes - 1), &need);
+    return carve(m, "hmmr_predict_video", p.n, imin(p.n, p.max_frames), p.T, need, out);
+}
+
+// several tracks, n_frames > 0.  A tail pass may end inside a track's last, short window, so the kept-row count varies from pass to
+// pass: every pass is asked (a stage's query runs only when the pass's sizes differ from the pass before).
+int carve_tracks(const hmmr_model_t* m, const int32_t* off, int n_tracks, const hmmr_tracks_plan_t& p, Carve* out) {
+    TailNeeds need = {};
+    TailPass last = {0, -1, 0, -1};
+    for (int i = 0; i < p.tail_passes; ++i) {
+        TailPass t;
+        if (hmmr_tracks_tail_pass(off, n_tracks, &p, i, &t.w0, &t.nw, &t.o0, &t.keep)) return -1;
+        if (t.nw != last.nw || t.keep != last.keep) tail_needs_add(m, p.T, t, &need);
+        last = t;
+    }
+    return carve(m, "hmmr_predict_tracks", p.n_frames, imin(p.n_frames, p.max_frames), p.T, need, out);
+}
+
+// the record: every field of every container ends inside it
+int check_record(const hmmr_model_t* model, const int32_t* field_offsets, int64_t ld_rec, const char* who) {
+    VIDEO_REQUIRE(field_offsets, "%s: null field_offsets", who);
+    const int64_t K = model->smpl->num_kps, V = model->smpl->num_verts;
+    const int64_t size[7] = {3, 3 * K, 2 * K, 24 * 9, 10, 3 * V, 85};
+    for (int r = 0; r < model->ief->num_regressors; ++r)
+        for (int f = 0; f < 7; ++f) {
+            const int64_t o = field_offsets[r * 7 + f];
+            VIDEO_REQUIRE(o >= 0 && o + size[f] <= ld_rec, "%s: field %d of container %d (offset %lld, %lld floats) does not fit ld_rec=%lld", who,
+                          f, r, (long long)o, (long long)size[f], (long long)ld_rec);
+        }
+    return 0;
+}
+
+// the unit table against both pass sizes the ResNet will see (hmmr_resnet50_plan: host only); last = frames of the last pass
+int check_units(const hmmr_model_t* model, int last, int passes, int max_frames) {
+    hmmr_unit_plan_t units[HMMR_RESNET_UNITS];
+    if (hmmr_resnet50_plan(model->resnet, last + 1, units)) return -1;
+    if (passes > 1 && hmmr_resnet50_plan(model->resnet, max_frames, units)) return -1;
+    return 0;
+}
+
+// ResNet passes over n frames into phi [n + 1][C]; the zero image rides on the last pass
+int resnet_passes(const hmmr_model_t* model, const float* images, int n, int max_frames, int passes, float* phi, char* region, const Carve& c,
+                  void* stream) {
+    for (int i = 0; i < passes; ++i) {
+        const int f0 = i * max_frames, nf = imin(max_frames, n - f0), n_zero = i == passes - 1;
+        if (hmmr_resnet50_fwd(model->resnet, images + (size_t)f0 * 224 * 224 * 3, nf, n_zero, phi + (size_t)f0 * C, region, c.resnet_bytes,
+                              stream, nullptr))
+            return -2;
+    }
     return 0;
 }
 
@@ -104,7 +167,7 @@ extern "C" size_t hmmr_predict_video_workspace_bytes(const hmmr_model_t* model, 
         return 0;
     Carve c;
     if (p.n == 0) p.n = 1, p.n_windows = p.resnet_passes = p.tail_passes = 1;      // (an empty video needs nothing: report what one frame takes, never 0 for a good model)
-    return carve(model, p, &c) ? 0 : c.total;
+    return carve_video(model, p, &c) ? 0 : c.total;
 }
 
 extern "C" int hmmr_predict_video(const hmmr_model_t* model, const float* images, int n, float* rec, int64_t ld_rec,
@@ -113,40 +176,21 @@ extern "C" int hmmr_predict_video(const hmmr_model_t* model, const float* images
     if (check_model(model, "hmmr_predict_video")) return -1;
     hmmr_video_plan_t p;
     if (hmmr_video_plan(n, model->sequence_length, model->fov, max_frames, max_windows, &p)) return -1;
-    VIDEO_REQUIRE(field_offsets, "hmmr_predict_video: null field_offsets");
+    if (check_record(model, field_offsets, ld_rec, "hmmr_predict_video")) return -1;
     const int R = model->ief->num_regressors;
-    {   // the record: every field of every container ends inside it
-        const int64_t K = model->smpl->num_kps, V = model->smpl->num_verts;
-        const int64_t size[7] = {3, 3 * K, 2 * K, 24 * 9, 10, 3 * V, 85};
-        for (int r = 0; r < R; ++r)
-            for (int f = 0; f < 7; ++f) {
-                const int64_t o = field_offsets[r * 7 + f];
-                VIDEO_REQUIRE(o >= 0 && o + size[f] <= ld_rec, "hmmr_predict_video: field %d of container %d (offset %lld, %lld floats) does not fit ld_rec=%lld",
-                              f, r, (long long)o, (long long)size[f], (long long)ld_rec);
-            }
-    }
     if (n == 0) return 0;
     VIDEO_REQUIRE(images && rec && ws, "hmmr_predict_video: null images, rec or ws");
     VIDEO_REQUIRE(((uintptr_t)ws & 255u) == 0, "hmmr_predict_video: ws must be 256-byte aligned");
     VIDEO_REQUIRE(((uintptr_t)images & 15u) == 0, "hmmr_predict_video: images must be 16-byte aligned (hmmr_resnet50_fwd reads them as aligned groups of 4 floats)");
     Carve c;
-    if (carve(model, p, &c)) return -1;
+    if (carve_video(model, p, &c)) return -1;
     VIDEO_REQUIRE(ws_bytes >= c.total, "hmmr_predict_video: workspace too small (%zu < %zu)", ws_bytes, c.total);
-    {   // the unit table against both pass sizes the ResNet will see (hmmr_resnet50_plan: host only)
-        hmmr_unit_plan_t units[HMMR_RESNET_UNITS];
-        if (hmmr_resnet50_plan(model->resnet, resnet_pass_frames(p, p.resnet_passes - 1) + 1, units)) return -1;
-        if (p.resnet_passes > 1 && hmmr_resnet50_plan(model->resnet, p.max_frames, units)) return -1;
-    }
+    if (check_units(model, p.n - (p.resnet_passes - 1) * p.max_frames, p.resnet_passes, p.max_frames)) return -1;
 
     char* base = (char*)ws;
     float* phi = (float*)(base + c.phi);
     char* region = base + c.region;
-    for (int i = 0; i < p.resnet_passes; ++i) {
-        const int f0 = i * p.max_frames, nf = resnet_pass_frames(p, i), n_zero = i == p.resnet_passes - 1;
-        if (hmmr_resnet50_fwd(model->resnet, images + (size_t)f0 * 224 * 224 * 3, nf, n_zero, phi + (size_t)f0 * C, region, c.resnet_bytes,
-                              stream, nullptr))
-            return -2;
-    }
+    if (resnet_passes(model, images, p.n, p.max_frames, p.resnet_passes, phi, region, c, stream)) return -2;
     float* windows = (float*)(region + c.windows);
     float* strips = (float*)(region + c.strips);
     float* kept = (float*)(region + c.kept);
@@ -160,6 +204,65 @@ extern "C" int hmmr_predict_video(const hmmr_model_t* model, const float* images
             return -2;
         }
         if (hmmr_keep_rows(strips, t.w0, t.nw, p.T, p.margin, p.g, C, p.n, kept, C, stream)) return -2;
+        if (hmmr_ief_fwd(model->ief, kept, t.keep, omegas, region + c.ief_ws, c.ief_bytes, stream)) return -2;
+        if (hmmr_smpl_fwd_records(model->smpl, omegas, R, t.keep, rec + (size_t)t.o0 * (size_t)ld_rec, ld_rec, field_offsets,
+                                  region + c.smpl_ws, c.smpl_bytes, stream))
+            return -2;
+    }
+    return 0;
+}
+
+extern "C" size_t hmmr_predict_tracks_workspace_bytes(const hmmr_model_t* model, const int32_t* track_offsets, int n_tracks, int max_frames,
+                                                      int max_windows) {
+    hmmr_tracks_plan_t p;
+    if (check_model(model, "hmmr_predict_tracks_workspace_bytes") ||
+        hmmr_tracks_plan(track_offsets, n_tracks, model->sequence_length, model->fov, max_frames, max_windows, &p))
+        return 0;
+    Carve c;
+    if (p.n_frames == 0) {                                 // (nothing to run needs nothing: report what one frame takes, never 0 for a good model)
+        const int32_t one[2] = {0, 1};
+        if (hmmr_tracks_plan(one, 1, model->sequence_length, model->fov, max_frames, max_windows, &p)) return 0;
+        return carve_tracks(model, one, 1, p, &c) ? 0 : c.total;
+    }
+    return carve_tracks(model, track_offsets, n_tracks, p, &c) ? 0 : c.total;
+}
+
+extern "C" int hmmr_predict_tracks(const hmmr_model_t* model, const float* images, const int32_t* track_offsets, int n_tracks, float* rec,
+                                   int64_t ld_rec, const int32_t* field_offsets, int max_frames, int max_windows, void* ws, size_t ws_bytes,
+                                   void* stream) {
+    if (check_model(model, "hmmr_predict_tracks")) return -1;
+    hmmr_tracks_plan_t p;
+    if (hmmr_tracks_plan(track_offsets, n_tracks, model->sequence_length, model->fov, max_frames, max_windows, &p)) return -1;
+    if (check_record(model, field_offsets, ld_rec, "hmmr_predict_tracks")) return -1;
+    const int R = model->ief->num_regressors;
+    if (p.n_frames == 0) return 0;
+    VIDEO_REQUIRE(images && rec && ws, "hmmr_predict_tracks: null images, rec or ws");
+    VIDEO_REQUIRE(((uintptr_t)ws & 255u) == 0, "hmmr_predict_tracks: ws must be 256-byte aligned");
+    VIDEO_REQUIRE(((uintptr_t)images & 15u) == 0, "hmmr_predict_tracks: images must be 16-byte aligned (hmmr_resnet50_fwd reads them as aligned groups of 4 floats)");
+    Carve c;
+    if (carve_tracks(model, track_offsets, n_tracks, p, &c)) return -1;
+    VIDEO_REQUIRE(ws_bytes >= c.total, "hmmr_predict_tracks: workspace too small (%zu < %zu)", ws_bytes, c.total);
+    if (check_units(model, p.n_frames - (p.resnet_passes - 1) * p.max_frames, p.resnet_passes, p.max_frames)) return -1;
+
+    char* base = (char*)ws;
+    float* phi = (float*)(base + c.phi);
+    char* region = base + c.region;
+    if (resnet_passes(model, images, p.n_frames, p.max_frames, p.resnet_passes, phi, region, c, stream)) return -2;
+    float* windows = (float*)(region + c.windows);
+    float* strips = (float*)(region + c.strips);
+    float* kept = (float*)(region + c.kept);
+    float* omegas = (float*)(region + c.omegas);
+    for (int i = 0; i < p.tail_passes; ++i) {
+        TailPass t;
+        if (hmmr_tracks_tail_pass(track_offsets, n_tracks, &p, i, &t.w0, &t.nw, &t.o0, &t.keep)) return -2;      // (carve_tracks walked every pass: cannot fail)
+        if (hmmr_gather_windows_tracks(phi, phi + (size_t)p.n_frames * C, track_offsets, n_tracks, t.w0, t.nw, p.T, p.margin, p.g, C, windows, stream))
+            return -2;
+        if (model->temporal) {
+            if (hmmr_temporal_fwd(model->temporal, windows, t.nw, p.T, strips, region + c.movie_ws, c.movie_bytes, stream)) return -2;
+        } else if (hmmr_hallucinator_fwd(model->hallucinator, windows, t.nw * p.T, strips, region + c.movie_ws, c.movie_bytes, stream)) {
+            return -2;
+        }
+        if (hmmr_keep_rows_tracks(strips, track_offsets, n_tracks, t.w0, t.nw, p.T, p.margin, p.g, C, kept, C, stream)) return -2;
         if (hmmr_ief_fwd(model->ief, kept, t.keep, omegas, region + c.ief_ws, c.ief_bytes, stream)) return -2;
         if (hmmr_smpl_fwd_records(model->smpl, omegas, R, t.keep, rec + (size_t)t.o0 * (size_t)ld_rec, ld_rec, field_offsets,
                                   region + c.smpl_ws, c.smpl_bytes, stream))

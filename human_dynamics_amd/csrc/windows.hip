@@ -5,6 +5,7 @@
 // Both are pure copies: a wave moves 1 KiB of one row per instruction (16 bytes per lane, consecutive lanes consecutive pieces); a
 // workgroup of four waves works on four rows at a time, so short rows (c = 8) still fill it.  HBM-bound: 8 bytes moved per float.
 // Every offset is 64-bit (n * c passes 2^31 for long videos); the row -> (window, slot) division happens once per row, not per piece.
+// hmmr_gather_windows_tracks / hmmr_keep_rows_tracks are the same two copies over several tracks laid end to end, for hmmr_predict_tracks.
 #include "common.h"
 #include "hmmr_hip.h"
 
@@ -36,6 +37,66 @@ keep_rows_kernel(const f32x4* __restrict__ strips, long long rows, int T, int ma
         f32x4* dst = out + r * ld4;
         for (int i = threadIdx.x; i < c4; i += HMMR_WAVE) dst[i] = src[i];
     }
+}
+
+// ---- the ragged form: several tracks along the frame axis, each with its own padding, window grid and kept rows (include/hmmr_hip.h)
+constexpr int TRACK_CHUNK = 64;                 // tracks per launch: their offsets and window bases are kernel arguments (as csrc/track.hip)
+struct TrackTable { int n; int off[TRACK_CHUNK + 1]; int win[TRACK_CHUNK + 1]; };      // absolute frames / absolute windows; entries past n repeat the last
+
+// A row belongs to one wave (threadIdx.y), so its number is wave-uniform; saying so keeps the track search in scalar registers, the
+// table in the kernel-argument segment (scalar loads, no scratch copy) and the lane loop below free of it.
+__device__ __forceinline__ int wave_row() { return __builtin_amdgcn_readfirstlane((int)threadIdx.y); }
+// the k in [0, n) with edge[k] <= v < edge[k + 1], for edge[0] <= v < edge[n]; entries that repeat (empty tracks) are stepped over
+__device__ __forceinline__ int track_of(const int* edge, int n, int v) {
+    int lo = 0, hi = n - 1;
+    while (lo < hi) {
+        const int mid = (lo + hi) >> 1;
+        if (edge[mid + 1] <= v) lo = mid + 1; else hi = mid;
+    }
+    return lo;
+}
+
+// out row r = (global window first + r / T, slot r % T) of the windows [first, first + rows / T), all of them owned by tracks of tt
+__global__ void __launch_bounds__(HMMR_WAVE * ROWS_PER_BLOCK)
+gather_windows_tracks_kernel(const f32x4* __restrict__ phi, const f32x4* __restrict__ phi_zero, TrackTable tt, int first, long long rows,
+                             int T, int margin, int g, int c4, f32x4* __restrict__ out) {
+    for (long long r = (long long)blockIdx.x * ROWS_PER_BLOCK + wave_row(); r < rows; r += (long long)gridDim.x * ROWS_PER_BLOCK) {
+        const long long wl = r / T;
+        const int w = first + (int)wl, t = (int)(r - wl * T);
+        const int k = track_of(tt.win, tt.n, w);
+        const long long f = (long long)(w - tt.win[k]) * g + t - margin;
+        const f32x4* src = (f >= 0 && f < tt.off[k + 1] - tt.off[k]) ? phi + (tt.off[k] + f) * c4 : phi_zero;
+        f32x4* dst = out + r * c4;
+        for (int i = threadIdx.x; i < c4; i += HMMR_WAVE) dst[i] = src[i];
+    }
+}
+
+// out row r is frame first + r, one of tt's: frame f of track k sits in local window f / g at slot margin + f % g; strips starts at global window w0
+__global__ void __launch_bounds__(HMMR_WAVE * ROWS_PER_BLOCK)
+keep_rows_tracks_kernel(const f32x4* __restrict__ strips, TrackTable tt, int first, int rows, int w0, int T, int margin, int g, int c4,
+                        f32x4* __restrict__ out, long long ld4) {
+    for (long long r = (long long)blockIdx.x * ROWS_PER_BLOCK + wave_row(); r < rows; r += (long long)gridDim.x * ROWS_PER_BLOCK) {
+        const int frame = first + (int)r;
+        const int k = track_of(tt.off, tt.n, frame);
+        const int f = frame - tt.off[k], lw = f / g;
+        const f32x4* src = strips + ((long long)(tt.win[k] + lw - w0) * T + margin + (f - lw * g)) * c4;
+        f32x4* dst = out + r * ld4;
+        for (int i = threadIdx.x; i < c4; i += HMMR_WAVE) dst[i] = src[i];
+    }
+}
+
+// tracks [t0, t0 + n) of the table; base = the global number of track t0's first window
+TrackTable table_at(const int32_t* off, int n_tracks, int t0, int g, int base) {
+    TrackTable tt;
+    tt.n = n_tracks - t0 < TRACK_CHUNK ? n_tracks - t0 : TRACK_CHUNK;
+    tt.off[0] = off[t0];
+    tt.win[0] = base;
+    for (int t = 1; t <= TRACK_CHUNK; ++t) {
+        const int k = t0 + (t < tt.n ? t : tt.n);
+        tt.off[t] = off[k];
+        tt.win[t] = tt.win[t - 1] + (int)(((long long)tt.off[t] - tt.off[t - 1] + g - 1) / g);
+    }
+    return tt;
 }
 
 inline bool aligned16(const void* p) { return ((uintptr_t)p & 15u) == 0; }
@@ -79,5 +140,68 @@ extern "C" int hmmr_keep_rows(const float* strips, int w0, int n_windows, int T,
     hipLaunchKernelGGL(keep_rows_kernel, dim3(blocks_for(rows)), dim3(HMMR_WAVE, ROWS_PER_BLOCK), 0, (hipStream_t)stream,
                        (const f32x4*)strips, rows, T, margin, g, c / 4, (f32x4*)out, (long long)(ld_out / 4));
     HMMR_CHECK_HIP(hipGetLastError());
+    return 0;
+}
+
+int hmmr_tracks_check_offsets(const char* who, const int32_t* off, int n_tracks);       // csrc/video_plan.cpp
+
+extern "C" int hmmr_gather_windows_tracks(const float* phi, const float* phi_zero, const int32_t* track_offsets, int n_tracks, int w0,
+                                          int n_windows, int T, int margin, int g, int c, float* out, void* stream) {
+    const char* who = "hmmr_gather_windows_tracks";
+    if (hmmr_tracks_check_offsets(who, track_offsets, n_tracks)) return -1;
+    HMMR_REQUIRE(w0 >= 0 && n_windows >= 0, "%s: w0=%d and n_windows=%d must not be negative", who, w0, n_windows);
+    HMMR_REQUIRE(T >= 1 && margin >= 0 && g >= 1 && (long long)margin + g <= T,
+                 "%s: bad window (T=%d, margin=%d, g=%d: need g >= 1 and margin + g <= T)", who, T, margin, g);
+    HMMR_REQUIRE(c >= 4 && c % 4 == 0, "%s: c=%d must be a positive multiple of 4 (16-byte pieces)", who, c);
+    if (n_windows == 0) return 0;
+    const long long w1 = (long long)w0 + n_windows;
+    {   // the range lies inside the numbering (checked before the first launch: a later chunk cannot refuse)
+        long long total = 0;
+        for (int k = 0; k < n_tracks; ++k) total += ((long long)track_offsets[k + 1] - track_offsets[k] + g - 1) / g;
+        HMMR_REQUIRE(w1 <= total, "%s: windows [%d, %lld) leave the %lld windows of these tracks", who, w0, w1, total);
+    }
+    HMMR_REQUIRE(phi && phi_zero && out, "%s: null argument", who);
+    HMMR_REQUIRE(aligned16(phi) && aligned16(phi_zero) && aligned16(out), "%s: pointers must be 16-byte aligned", who);
+    int base = 0;
+    for (int t0 = 0; t0 < n_tracks && base < w1; t0 += TRACK_CHUNK) {
+        const TrackTable tt = table_at(track_offsets, n_tracks, t0, g, base);
+        base = tt.win[tt.n];
+        const long long a = w0 > tt.win[0] ? w0 : tt.win[0], b = w1 < base ? w1 : base;      // this chunk's share of the range
+        if (a >= b) continue;
+        const long long rows = (b - a) * T;
+        hipLaunchKernelGGL(gather_windows_tracks_kernel, dim3(blocks_for(rows)), dim3(HMMR_WAVE, ROWS_PER_BLOCK), 0, (hipStream_t)stream,
+                           (const f32x4*)phi, (const f32x4*)phi_zero, tt, (int)a, rows, T, margin, g, c / 4,
+                           (f32x4*)out + (a - w0) * T * (c / 4));
+        HMMR_CHECK_HIP(hipGetLastError());
+    }
+    return 0;
+}
+
+extern "C" int hmmr_keep_rows_tracks(const float* strips, const int32_t* track_offsets, int n_tracks, int w0, int n_windows, int T,
+                                     int margin, int g, int c, float* out, int64_t ld_out, void* stream) {
+    const char* who = "hmmr_keep_rows_tracks";
+    if (hmmr_tracks_check_offsets(who, track_offsets, n_tracks)) return -1;
+    HMMR_REQUIRE(w0 >= 0 && n_windows >= 0, "%s: w0=%d and n_windows=%d must not be negative", who, w0, n_windows);
+    HMMR_REQUIRE(T >= 1 && margin >= 0 && g >= 1 && (long long)margin + g <= T,
+                 "%s: bad window (T=%d, margin=%d, g=%d: need g >= 1 and margin + g <= T)", who, T, margin, g);
+    HMMR_REQUIRE(c >= 4 && c % 4 == 0 && ld_out >= c && ld_out % 4 == 0,
+                 "%s: c=%d and ld_out=%lld must be multiples of 4 with ld_out >= c (16-byte pieces)", who, c, (long long)ld_out);
+    if (n_windows == 0) return 0;
+    int o0, keep;
+    if (hmmr_tracks_window_rows(track_offsets, n_tracks, g, w0, n_windows, &o0, &keep)) return -1;      // refuses a range that leaves the numbering
+    HMMR_REQUIRE(strips && out, "%s: null argument", who);
+    HMMR_REQUIRE(aligned16(strips) && aligned16(out), "%s: pointers must be 16-byte aligned", who);
+    const long long o1 = (long long)o0 + keep;
+    int base = 0;
+    for (int t0 = 0; t0 < n_tracks && track_offsets[t0] < o1; t0 += TRACK_CHUNK) {
+        const TrackTable tt = table_at(track_offsets, n_tracks, t0, g, base);
+        base = tt.win[tt.n];
+        const long long a = o0 > tt.off[0] ? o0 : tt.off[0], b = o1 < tt.off[tt.n] ? o1 : tt.off[tt.n];      // this chunk's share of the rows
+        if (a >= b) continue;
+        hipLaunchKernelGGL(keep_rows_tracks_kernel, dim3(blocks_for(b - a)), dim3(HMMR_WAVE, ROWS_PER_BLOCK), 0, (hipStream_t)stream,
+                           (const f32x4*)strips, tt, (int)a, (int)(b - a), w0, T, margin, g, c / 4, (f32x4*)out + (a - o0) * (ld_out / 4),
+                           (long long)(ld_out / 4));
+        HMMR_CHECK_HIP(hipGetLastError());
+    }
     return 0;
 }

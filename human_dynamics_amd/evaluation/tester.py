@@ -482,13 +482,73 @@ class Tester(object):
             return {k: v.float().cpu().numpy() for k, v in unpack_outputs(rec, layout).items() if want is None or k in want}
         return self._guard_saturation(run)
 
-    def predict_videos(self, videos, want=None):
+    def predict_tracks(self, tracks, want=None, records=False, max_frames=MAX_DEVICE_FRAMES, max_windows=MAX_TAIL_WINDOWS):
+        """Every tracked person of a video through ONE call of the library (hmmr_predict_tracks, include/hmmr_hip.h): the tracks' frames
+        are laid end to end on the device (torch.cat: plumbing), the ResNet passes run over all of them, and every tail pass holds windows
+        of several tracks -- each track with its own zero-image padding, window grid and kept rows -- so a crowd of short tracks runs as
+        few large launches instead of one set of small ones per person.  Track k's result is, byte for byte, what predict_all_images
+        gives for it alone.
+
+        tracks: a list of [N_i,224,224,3] float32 arrays in [-1,1], host or device (what run_video.process_tracks returns); N_i = 0 is
+        legal.  uint8 crops are refused: they go through predict_videos' streamed path.
+        Returns the list of dicts predict_all_images returns (`want`: a subset of the keys).  records=True: (views, layout) instead --
+        per track the [N_i, rec_len] device view of the ONE record buffer, and the layout of Tester.record_layout(); (view, layout,
+        (start, end), image_og_params) is a track of util/render/video.render_scene and run_video.render_tracks, so process_tracks ->
+        predict_tracks -> render_tracks leaves the device only for the PNGs.
+        max_frames / max_windows: frames per ResNet pass and windows per tail pass; they bound the workspace and change no bit.
+        The call runs inside the saturation guard: if any split-fp16 store of the batch clamps a value, the WHOLE batch is repeated
+        with fp32 operands (and the Tester keeps them); the equality with the per-track loop holds for calls that raise no flag."""
+        import ctypes as C
+        from ..dist import unpack_outputs
+        from ..engine import _Workspace
+        tracks = list(tracks)
+        max_frames, max_windows = int(max_frames), int(max_windows)
+        for k, trk in enumerate(tracks):
+            if (trk.dtype == torch.uint8) if isinstance(trk, torch.Tensor) else (np.asarray(trk).dtype == np.uint8):
+                raise ValueError("track %d: uint8 input goes through the streamed path (predict_videos / predict_all_images, stream=True)" % k)
+            if len(trk) and tuple(trk.shape[1:]) != (224, 224, 3):
+                raise ValueError("track %d: frames of shape %s, need [N,224,224,3]" % (k, tuple(trk.shape)))
+
+        def run():
+            eng = self.engine
+            model = self.native_model()
+            parts = [eng.to_device(trk).reshape(-1, 224, 224, 3) for trk in tracks if len(trk)]
+            offsets = np.zeros(len(tracks) + 1, np.int32)
+            np.cumsum([len(trk) for trk in tracks], out=offsets[1:])
+            n = int(offsets[-1])
+            off_p = offsets.ctypes.data_as(C.POINTER(C.c_int32))
+            frames = parts[0] if len(parts) == 1 else torch.cat(parts, dim=0) if parts else None
+            R = eng.iw.num_regressors
+            offs, ld_rec = (C.c_int32 * (R * 7))(), C.c_int64(0)
+            L.check(eng.lib.hmmr_record_layout(eng.num_kps, eng.num_verts, R, offs, C.byref(ld_rec)), "hmmr_record_layout")
+            layout, rec_len = self.record_layout()
+            assert rec_len == ld_rec.value, (rec_len, ld_rec.value)
+            rec = torch.empty((n, rec_len), dtype=torch.float32, device=eng.device)
+            nbytes = eng.lib.hmmr_predict_tracks_workspace_bytes(C.byref(model), off_p, len(tracks), max_frames, max_windows)
+            if not nbytes:
+                L.check(-1, "hmmr_predict_tracks_workspace_bytes")
+            ws = eng._ws.setdefault("video", _Workspace(eng.device)).get(nbytes)
+            L.check(eng.lib.hmmr_predict_tracks(C.byref(model), frames.data_ptr() if n else None, off_p, len(tracks), rec.data_ptr() if n else None,
+                                                rec_len, offs, max_frames, max_windows, ws.data_ptr(), nbytes, eng._stream()),
+                    "hmmr_predict_tracks")
+            views = [rec[int(offsets[k]):int(offsets[k + 1])] for k in range(len(tracks))]
+            torch.cuda.synchronize(eng.device)          # (also for records: the guard reads the flags this call raised)
+            if records:
+                return views, layout
+            return [{k: v.float().cpu().numpy() for k, v in unpack_outputs(view, layout).items() if want is None or k in want} for view in views]
+        return self._guard_saturation(run)
+
+    def predict_videos(self, videos, want=None, batched=False):
         """`predict_all_images` for several videos at once -- how the demo is driven, one call per person track
         (/root/reference/demo_video.py:172, src/evaluation/tester.py:229-312): a list of host arrays [N_i,224,224,3] (float32 in
         [-1,1] or uint8 crops) -> a list of the dicts `predict_all_images` returns, each byte-identical to its own call.  The tracks run
         as ONE pipeline (evaluation/streaming.py: run_many): track k+1 uploads under track k's ResNet, track k's tail and download run
-        under track k+1's ResNet -- the sustained rate of the host-in / host-out surface instead of one isolated call's latency."""
+        under track k+1's ResNet -- the sustained rate of the host-in / host-out surface instead of one isolated call's latency.
+        batched=True: all tracks through one library call instead (`predict_tracks`: float32 crops, host or device); the default keeps
+        the route above, in which device tensors run one `predict_all_images` each."""
         videos = list(videos)
+        if batched:
+            return self.predict_tracks(videos, want)
         if self._uses_split_operands() and not getattr(self, "_in_guard", False):
             self._in_guard = True
             try:

@@ -1008,6 +1008,71 @@ int hmmr_predict_video(const hmmr_model_t* model, const float* images, int n, fl
                        const int32_t* field_offsets, int max_frames, int max_windows, void* ws, size_t ws_bytes,
                        void* stream);
 
+/* ------------------------------------------------------------------------- *
+ * Every tracked person of a video through one call (additive to ABI 19): the ragged form of the scheme above.
+ *
+ * Tracks lie one after the other along the frame axis, as for hmmr_track_bbox.  track_offsets: n_tracks + 1 non-decreasing
+ * int32 values in HOST memory, track_offsets[0] = 0; it is checked before anything is launched and reaches the kernels as
+ * kernel arguments, 64 tracks per launch: no device table, no upload, no synchronisation.  With off = track_offsets:
+ *   track k has n_k = off[k + 1] - off[k] frames (0 is legal) and W_k = ceil(n_k / g) windows;
+ *   windows are numbered globally, track after track: B_k = W_0 + ... + W_{k-1}, n_windows = B_{n_tracks};
+ *   gather: slot t of window B_k + lw holds phi[off[k] + f], f = lw g + t - margin, if 0 <= f < n_k, else phi_zero -- never a
+ *           frame of a neighbouring track: every track has its own zero-image padding;
+ *   keep:   for 0 <= j < min(g, n_k - lw g), slot margin + j of window B_k + lw is output row off[k] + lw g + j: the kept rows of
+ *           consecutive windows are consecutive (also across tracks), and the rows come out in global frame order.
+ * Rows [off[k], off[k + 1]) of the result are, byte for byte, what the one-video call writes for track k alone.
+ * ------------------------------------------------------------------------- */
+typedef struct {
+    int n_tracks, T, fov;        /* as given */
+    int margin, g;               /* (fov - 1) / 2, T - 2 margin */
+    int n_frames;                /* track_offsets[n_tracks] */
+    int n_windows;               /* sum of ceil(n_k / g) */
+    int max_frames, max_windows; /* as given */
+    int resnet_passes;           /* ceil(n_frames / max_frames) over the concatenated frames; the last one carries the zero image */
+    int tail_passes;             /* ceil(n_windows / max_windows): pass i runs global windows [i max_windows, min(n_windows, ...)) */
+} hmmr_tracks_plan_t;
+/* Host only, no HIP call.  Refused (-1): null track_offsets (also for n_tracks = 0: one value is read), n_tracks < 0,
+ * track_offsets[0] != 0, a decreasing pair (named), n_frames = INT32_MAX (row n_frames, the zero image's, would not be an
+ * int), fov even or < 1, g < 1, max_frames < 1, max_windows < 1.  No track or only empty ones: no window, no pass. */
+int hmmr_tracks_plan(const int32_t* track_offsets, int n_tracks, int T, int fov, int max_frames, int max_windows,
+                     hmmr_tracks_plan_t* out);
+/* Host only.  The owner of global window w: *track = k and *local_window = lw with w = B_k + lw (either may be NULL); -1 if w
+ * is not one of the n_windows.  hmmr_tracks_window_rows: the output rows of windows [w0, w0 + n_windows), n_windows >= 1 and all
+ * of them existing: *o0 = the first one's first kept row, *keep = how many rows they keep together.  hmmr_tracks_tail_pass:
+ * tail pass i of a plan, 0 <= i < tail_passes: its first window, its window count and the two values above. */
+int hmmr_tracks_window_owner(const int32_t* track_offsets, int n_tracks, int g, int w, int* track, int* local_window);
+int hmmr_tracks_window_rows(const int32_t* track_offsets, int n_tracks, int g, int w0, int n_windows, int* o0, int* keep);
+int hmmr_tracks_tail_pass(const int32_t* track_offsets, int n_tracks, const hmmr_tracks_plan_t* plan, int i, int* w0,
+                          int* n_windows, int* o0, int* keep);
+
+/* The two copies of the ragged rule (csrc/windows.hip): as hmmr_gather_windows / hmmr_keep_rows (16-byte pieces, 64-bit
+ * offsets, nothing allocated, refusals before the launch), for any range [w0, w0 + n_windows) of the global numbering --
+ * one that starts inside a track, spans empty tracks or crosses the 64-track boundary of the argument table included; a
+ * range that leaves the numbering is refused.  n_windows = 0: nothing is launched.
+ * hmmr_gather_windows_tracks: phi [n_frames][c], phi_zero [c] -> out [n_windows][T][c].
+ * hmmr_keep_rows_tracks: strips [n_windows][T][c] of the same windows -> the `keep` rows of hmmr_tracks_window_rows, the
+ *   first at `out` (= the result's row o0), ld_out floats apart; columns c .. ld_out - 1 and every other row are not touched. */
+int hmmr_gather_windows_tracks(const float* phi, const float* phi_zero, const int32_t* track_offsets, int n_tracks, int w0,
+                               int n_windows, int T, int margin, int g, int c, float* out, void* stream);
+int hmmr_keep_rows_tracks(const float* strips, const int32_t* track_offsets, int n_tracks, int w0, int n_windows, int T,
+                          int margin, int g, int c, float* out, int64_t ld_out, void* stream);
+
+/* hmmr_predict_tracks: images [n_frames,224,224,3], the tracks' frames one after the other -> rec [n_frames][ld_rec], row
+ * off[k] + f the record of frame f of track k.  hmmr_predict_video's rules hold: everything is queued on `stream`, nothing is
+ * allocated or synchronised, every check (track_offsets included) is made before the first launch, a refused call (-1) has
+ * queued nothing, -2 comes only from a stage.  No track or only empty ones: returns 0, queues nothing.
+ *   1. ResNet passes of at most max_frames of the concatenated frames; the zero image rides on the last one;
+ *   2. per tail pass (hmmr_tracks_tail_pass): hmmr_gather_windows_tracks, hmmr_temporal_fwd (or hmmr_hallucinator_fwd),
+ *      hmmr_keep_rows_tracks, hmmr_ief_fwd, hmmr_smpl_fwd_records into rec + o0 ld_rec.
+ * Windows of several tracks share a tail pass and frames of several tracks a ResNet pass: a crowd of short tracks runs as
+ * few large launches instead of many small ones.  The workspace (0: bad model, offsets or plan) is sized like
+ * hmmr_predict_video's, for n_frames frames and the largest tail pass. */
+size_t hmmr_predict_tracks_workspace_bytes(const hmmr_model_t* model, const int32_t* track_offsets, int n_tracks, int max_frames,
+                                           int max_windows);
+int hmmr_predict_tracks(const hmmr_model_t* model, const float* images, const int32_t* track_offsets, int n_tracks, float* rec,
+                        int64_t ld_rec, const int32_t* field_offsets, int max_frames, int max_windows, void* ws, size_t ws_bytes,
+                        void* stream);
+
 #ifdef __cplusplus
 }
 #endif
