@@ -145,6 +145,12 @@ __device__ __forceinline__ void split_flag_max(float m) {
 #endif
 }
 __device__ __forceinline__ bool split_overflows(float v) { return !(__builtin_fabsf(v) <= HMMR_SPLIT_MAX); }     // (+-inf and NaN included)
+// the flag(s) of a store that tests value by value: SATURATED for anything split_overflows() caught, + NAN when one of them was a NaN
+__device__ __forceinline__ void split_flag(bool bad, bool nan) {
+#ifndef HMMR_NO_SATURATION_CHECK
+    if (bad) atomicOr(&g_split_flags, nan ? (HMMR_FLAG_SATURATED | HMMR_FLAG_NAN) : HMMR_FLAG_SATURATED);
+#endif
+}
 typedef int (*hmmr_flag_reader_t)(unsigned* flags, int clear);
 void hmmr_register_flag_reader(hmmr_flag_reader_t fn);          // api.cpp
 namespace {

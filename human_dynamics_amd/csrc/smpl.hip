@@ -353,7 +353,7 @@ __global__ __launch_bounds__(256, 2) void smpl_verts_mfma_kernel(
 // at 22 operand bits (vertices within 1e-6 of the fp32 forms; the tolerance of the path is 1e-4).  The host packs the basis as
 // B-operand fragments (`dirs_split`: [K / 16][coordinate][hi, lo][k half][vertex][8 halves], pre-scaled by 2^13 so that the lo
 // halves of millimetre-sized blend-shape entries are normal fp16 numbers); the features are scaled by 2^8 and split into LDS here
-// (a feature beyond +-255 raises the saturation flag); the accumulator is scaled back by 2^-21 (exact).  D[instance][vertex]
+// (a feature beyond +-255 raises the saturation flag, a NaN feature the NaN flag with it); the accumulator is scaled back by 2^-21 (exact).  D[instance][vertex]
 // per coordinate as in the exact-fp32 form: a lane ends up with its vertex's blended position for 16 instances and runs the
 // (4-sparse, vector-unit) skinning sum unchanged.  Same 1-D, XCD-aware grid as smpl_verts_kernel.
 static constexpr int KCH = LDF / 16;     // 14 K chunks of 16 (rows >= 218 of the basis are zero)
@@ -388,7 +388,7 @@ __global__ __launch_bounds__(256, 2) void smpl_verts_split_kernel(
         const int ii = e / LDA;
         sA[ii][e % LDA] = (i0 + ii < m) ? A[(long long)(i0 + ii) * LDA + (e % LDA)] : 0.f;
     }
-    bool sat = false;
+    bool sat = false, nan = false;
     for (int e = threadIdx.x; e < IBM * KCH * 2; e += 256) {     // one 8-wide K group of one instance per step
         const int ii = e % IBM, g8 = e / IBM;                    // g8 = 2 kc + k half
         const float* f = feat + (long long)(i0 + ii) * LDF + g8 * 8;        // (the scratch rows are sized for m rounded up to IBM)
@@ -397,6 +397,7 @@ __global__ __launch_bounds__(256, 2) void smpl_verts_split_kernel(
         for (int j = 0; j < 8; ++j) {
             const float x = f[j] * FEAT_SPLIT_SCALE;
             sat = sat || (split_overflows(x) && i0 + ii < m);          // (rows beyond m are scratch)
+            nan = nan || (x != x && i0 + ii < m);                      // a NaN pose or shape: the clamp below would make it a finite number
             const float c = split_clamp(x);
             hi[j] = (shalf_t)c;
             lo[j] = (shalf_t)(c - (float)hi[j]);
@@ -404,7 +405,7 @@ __global__ __launch_bounds__(256, 2) void smpl_verts_split_kernel(
         sF[((g8 >> 1) * 2 + 0) * 2 * IBM + (g8 & 1) * IBM + ii] = hi;
         sF[((g8 >> 1) * 2 + 1) * 2 * IBM + (g8 & 1) * IBM + ii] = lo;
     }
-    split_flag(sat);
+    split_flag(sat, nan);
     // B fragments of chunk kc: [kc][c][plane][lh][vertex]; this lane's vertex = its column of D (v < vpad always)
     int v = t0 * VT + wave * 32 + lc;
     constexpr int PF = 2;                                        // K chunks requested ahead (PF + 1 register sets of 24)

@@ -317,3 +317,69 @@ def test_stem_entry_refuses_before_anything_is_queued():
     assert rc == -1 and b"hmmr_resnet50_fwd" in msg and b"stem.scale" in msg, (rc, msg)
     rc, msg = fwd(_stem_table(5))
     assert rc == -1 and b"bad dtype" in msg, (rc, msg)
+
+
+def test_smpl_entries_refuse_before_anything_is_queued():
+    """hmmr_smpl_fwd / _strided / _records: every refusal of csrc/smpl.hip's launcher, with dummy (never dereferenced) pointers and no
+    device -- the valid calls are what tests/test_gpu_smpl.py sweeps."""
+    import ctypes as C
+    lib = _lib.load()
+    P = [0x10000 * (i + 1) for i in range(8)]
+    BIG = 1 << 40
+
+    def consts(**kw):
+        sc = _lib.SmplConsts()
+        sc.num_verts, sc.num_kps, sc.lbs_nnz, sc.vpad = 170, 25, 4, 256
+        for name, _ in _lib.SmplConsts._fields_[4:]:
+            setattr(sc, name, 0x100000)
+        for k, v in kw.items():
+            setattr(sc, k, v)
+        return sc
+
+    def fwd(sc=None, theta=P[0], beta=P[1], cams=P[2], m=5, verts=P[3], joints=P[4], kps=P[5], rs=P[6], ws=P[7], ws_bytes=BIG, strided=False):
+        sc = consts() if sc is None else sc
+        head = (C.byref(sc) if sc else None, theta, 72, beta, 10, cams, 3, m, verts, joints, kps, rs)
+        if strided:
+            return lib.hmmr_smpl_fwd_strided(*head, 1000, ws, ws_bytes, None)
+        return lib.hmmr_smpl_fwd(*head, ws, ws_bytes, None)
+
+    def refused(rc, *words):
+        msg = lib.hmmr_last_error()
+        assert rc != 0 and msg, (rc, msg)
+        for w in words:
+            assert w in msg, (w, msg)
+
+    for strided in (False, True):
+        refused(fwd(m=0, strided=strided), b"hmmr_smpl_fwd", b"m must be positive")
+        refused(fwd(m=-3, strided=strided), b"m must be positive")
+        for bad in (0, -1, 25):
+            refused(fwd(consts(lbs_nnz=bad), strided=strided), b"lbs_nnz=%d out of range" % bad)
+        refused(fwd(consts(lbs_nnz=24), cams=None, strided=strided), b"kps requested without cams")      # (24 itself is a valid width)
+        refused(fwd(cams=None, strided=strided), b"kps requested without cams")
+        for vpad in (0, 128, 170, 250, 257, 320):            # below the vertex count rounded up to 128, or no multiple of 128
+            refused(fwd(consts(vpad=vpad), strided=strided), b"vpad=%d" % vpad, b"num_verts=170")
+        need = lib.hmmr_smpl_workspace_bytes(5)
+        assert need == lib.hmmr_smpl_workspace_bytes(32) > 0 and lib.hmmr_smpl_workspace_bytes(33) == lib.hmmr_smpl_workspace_bytes(64) > need
+        assert lib.hmmr_smpl_workspace_bytes(0) == 0 and lib.hmmr_smpl_workspace_bytes(-1) == 0
+        refused(fwd(ws_bytes=need - 1, strided=strided), b"workspace too small")
+        for missing in ("theta", "beta", "verts", "joints", "ws"):
+            refused(fwd(strided=strided, **{missing: None}), b"null argument")
+    refused(lib.hmmr_smpl_fwd(None, P[0], 72, P[1], 10, P[2], 3, 5, P[3], P[4], P[5], P[6], P[7], BIG, None), b"null argument")
+
+    def records(sc=None, om=P[0], R=3, n=21, rec=P[1], ld=2000, offs=None, ws=P[7]):
+        sc = consts() if sc is None else sc
+        offs = [90 * i for i in range(7 * max(R, 1))] if offs is None else offs
+        arr = (C.c_int32 * len(offs))(*offs)
+        return lib.hmmr_smpl_fwd_records(C.byref(sc), om, R, n, rec, ld, arr, ws, BIG, None)
+
+    refused(records(R=0), b"hmmr_smpl_fwd_records", b"bad container count")
+    refused(records(R=9, ld=1 << 20), b"bad container count")
+    refused(records(n=0), b"bad container count")
+    refused(records(om=None), b"null argument")
+    refused(records(rec=None), b"null argument")
+    for bad in (-1, 2000, 2001):
+        offs = [90 * i for i in range(21)]
+        offs[9] = bad
+        refused(records(offs=offs), b"field offset outside the record")
+    refused(records(sc=consts(vpad=320)), b"vpad=320")
+    refused(records(sc=consts(lbs_nnz=25)), b"lbs_nnz=25")
