@@ -1,8 +1,9 @@
-// hmmr_predict_video and hmmr_predict_tracks (include/hmmr_hip.h): Tester.predict_all_images (src/evaluation/tester.py:260-312) as ONE call of the C ABI -- the
-// frames of a video on the device in, the packed per-frame records on the device out, no Python and no torch in between.  The call
-// only sequences the stage entry points on the caller's stream: ResNet passes into phi, then per tail pass gather -> f_movie (or the
-// hallucinator) -> keep -> IEF -> SMPL records.  It owns no kernel and makes no HIP call itself; every check that a stage would make
-// is made here first, for every pass, so that a refused call has queued nothing.
+// hmmr_predict_tracks and hmmr_predict_video (include/hmmr_hip.h): Tester.predict_all_images (src/evaluation/tester.py:260-312) as ONE call of the C ABI -- the
+// frames of every track on the device in, the packed per-frame records on the device out, no Python and no torch in between.  There is
+// one driver, over tracks; a video is the one-track case {0, n}.  The call only sequences the stage entry points on the caller's
+// stream: ResNet passes into phi, then per tail pass gather -> f_movie (or the hallucinator) -> keep -> IEF -> SMPL records.  It owns no
+// kernel and makes no HIP call itself; every check that a stage would make is made here first, for every pass, so that a refused call
+// has queued nothing.
 #include <stddef.h>
 #include <stdint.h>
 
@@ -11,6 +12,8 @@
 #include "hmmr_hip.h"
 
 void hmmr_set_error(const char* fmt, ...);
+int hmmr_tracks_plan_as(const char* who, const int32_t* track_offsets, int n_tracks, int T, int fov, int max_frames, int max_windows,
+                        hmmr_tracks_plan_t* out);      // csrc/video_plan.cpp: hmmr_tracks_plan with the refusals under the caller's name
 
 #define VIDEO_REQUIRE(cond, ...) do { if (!(cond)) { hmmr_set_error(__VA_ARGS__); return -1; } } while (0)
 
@@ -29,16 +32,7 @@ struct Carve {
     size_t total;
 };
 
-struct TailPass { int w0, nw, o0, keep; };
-inline TailPass tail_pass(const hmmr_video_plan_t& p, int i) {
-    TailPass t;
-    t.w0 = i * p.max_windows;                            // (i < tail_passes: w0 < n_windows, no overflow)
-    t.nw = imin(p.max_windows, p.n_windows - t.w0);
-    const long long o0 = (long long)t.w0 * p.g, o1 = (long long)(t.w0 + t.nw) * p.g;
-    t.o0 = (int)o0;
-    t.keep = (int)((o1 < p.n ? o1 : (long long)p.n) - o0);
-    return t;
-}
+struct TailPass { int w0, nw, o0, keep; };      // hmmr_tracks_tail_pass
 
 // model pointers and everything the stages would refuse that does not depend on the frame count
 int check_model(const hmmr_model_t* m, const char* who) {
@@ -103,17 +97,9 @@ int carve(const hmmr_model_t* m, const char* who, int n, int resnet_frames, int 
     return 0;
 }
 
-// one video, n > 0.  The sizes of the first and of the last pass bound every pass between them (all but the last are full).
-int carve_video(const hmmr_model_t* m, const hmmr_video_plan_t& p, Carve* out) {
-    TailNeeds need = {};
-    tail_needs_add(m, p.T, tail_pass(p, 0), &need);
-    tail_needs_add(m, p.T, tail_pass(p, p.tail_passes - 1), &need);
-    return carve(m, "hmmr_predict_video", p.n, imin(p.n, p.max_frames), p.T, need, out);
-}
-
-// several tracks, n_frames > 0.  A tail pass may end inside a track's last, short window, so the kept-row count varies from pass to
-// pass: every pass is asked (a stage's query runs only when the pass's sizes differ from the pass before).
-int carve_tracks(const hmmr_model_t* m, const int32_t* off, int n_tracks, const hmmr_tracks_plan_t& p, Carve* out) {
+// n_frames > 0.  A tail pass may end inside a track's last, short window, so the kept-row count varies from pass to pass: every pass is
+// asked (a stage's query runs only when the pass's sizes differ from the pass before: for one track, the first pass and the last).
+int carve_tracks(const hmmr_model_t* m, const char* who, const int32_t* off, int n_tracks, const hmmr_tracks_plan_t& p, Carve* out) {
     TailNeeds need = {};
     TailPass last = {0, -1, 0, -1};
     for (int i = 0; i < p.tail_passes; ++i) {
@@ -122,7 +108,7 @@ int carve_tracks(const hmmr_model_t* m, const int32_t* off, int n_tracks, const 
         if (t.nw != last.nw || t.keep != last.keep) tail_needs_add(m, p.T, t, &need);
         last = t;
     }
-    return carve(m, "hmmr_predict_tracks", p.n_frames, imin(p.n_frames, p.max_frames), p.T, need, out);
+    return carve(m, who, p.n_frames, imin(p.n_frames, p.max_frames), p.T, need, out);
 }
 
 // the record: every field of every container ends inside it
@@ -159,89 +145,32 @@ int resnet_passes(const hmmr_model_t* model, const float* images, int n, int max
     return 0;
 }
 
-}  // namespace
-
-extern "C" size_t hmmr_predict_video_workspace_bytes(const hmmr_model_t* model, int n, int max_frames, int max_windows) {
-    hmmr_video_plan_t p;
-    if (check_model(model, "hmmr_predict_video_workspace_bytes") || hmmr_video_plan(n, model->sequence_length, model->fov, max_frames, max_windows, &p))
-        return 0;
-    Carve c;
-    if (p.n == 0) p.n = 1, p.n_windows = p.resnet_passes = p.tail_passes = 1;      // (an empty video needs nothing: report what one frame takes, never 0 for a good model)
-    return carve_video(model, p, &c) ? 0 : c.total;
-}
-
-extern "C" int hmmr_predict_video(const hmmr_model_t* model, const float* images, int n, float* rec, int64_t ld_rec,
-                                  const int32_t* field_offsets, int max_frames, int max_windows, void* ws, size_t ws_bytes,
-                                  void* stream) {
-    if (check_model(model, "hmmr_predict_video")) return -1;
-    hmmr_video_plan_t p;
-    if (hmmr_video_plan(n, model->sequence_length, model->fov, max_frames, max_windows, &p)) return -1;
-    if (check_record(model, field_offsets, ld_rec, "hmmr_predict_video")) return -1;
-    const int R = model->ief->num_regressors;
-    if (n == 0) return 0;
-    VIDEO_REQUIRE(images && rec && ws, "hmmr_predict_video: null images, rec or ws");
-    VIDEO_REQUIRE(((uintptr_t)ws & 255u) == 0, "hmmr_predict_video: ws must be 256-byte aligned");
-    VIDEO_REQUIRE(((uintptr_t)images & 15u) == 0, "hmmr_predict_video: images must be 16-byte aligned (hmmr_resnet50_fwd reads them as aligned groups of 4 floats)");
-    Carve c;
-    if (carve_video(model, p, &c)) return -1;
-    VIDEO_REQUIRE(ws_bytes >= c.total, "hmmr_predict_video: workspace too small (%zu < %zu)", ws_bytes, c.total);
-    if (check_units(model, p.n - (p.resnet_passes - 1) * p.max_frames, p.resnet_passes, p.max_frames)) return -1;
-
-    char* base = (char*)ws;
-    float* phi = (float*)(base + c.phi);
-    char* region = base + c.region;
-    if (resnet_passes(model, images, p.n, p.max_frames, p.resnet_passes, phi, region, c, stream)) return -2;
-    float* windows = (float*)(region + c.windows);
-    float* strips = (float*)(region + c.strips);
-    float* kept = (float*)(region + c.kept);
-    float* omegas = (float*)(region + c.omegas);
-    for (int i = 0; i < p.tail_passes; ++i) {
-        const TailPass t = tail_pass(p, i);
-        if (hmmr_gather_windows(phi, p.n, phi + (size_t)p.n * C, t.w0, t.nw, p.T, p.margin, p.g, C, windows, stream)) return -2;
-        if (model->temporal) {
-            if (hmmr_temporal_fwd(model->temporal, windows, t.nw, p.T, strips, region + c.movie_ws, c.movie_bytes, stream)) return -2;
-        } else if (hmmr_hallucinator_fwd(model->hallucinator, windows, t.nw * p.T, strips, region + c.movie_ws, c.movie_bytes, stream)) {
-            return -2;
-        }
-        if (hmmr_keep_rows(strips, t.w0, t.nw, p.T, p.margin, p.g, C, p.n, kept, C, stream)) return -2;
-        if (hmmr_ief_fwd(model->ief, kept, t.keep, omegas, region + c.ief_ws, c.ief_bytes, stream)) return -2;
-        if (hmmr_smpl_fwd_records(model->smpl, omegas, R, t.keep, rec + (size_t)t.o0 * (size_t)ld_rec, ld_rec, field_offsets,
-                                  region + c.smpl_ws, c.smpl_bytes, stream))
-            return -2;
-    }
-    return 0;
-}
-
-extern "C" size_t hmmr_predict_tracks_workspace_bytes(const hmmr_model_t* model, const int32_t* track_offsets, int n_tracks, int max_frames,
-                                                      int max_windows) {
+size_t workspace_bytes(const char* who, const hmmr_model_t* model, const int32_t* off, int n_tracks, int max_frames, int max_windows) {
     hmmr_tracks_plan_t p;
-    if (check_model(model, "hmmr_predict_tracks_workspace_bytes") ||
-        hmmr_tracks_plan(track_offsets, n_tracks, model->sequence_length, model->fov, max_frames, max_windows, &p))
-        return 0;
-    Carve c;
+    if (check_model(model, who) || hmmr_tracks_plan_as(who, off, n_tracks, model->sequence_length, model->fov, max_frames, max_windows, &p)) return 0;
+    const int32_t one[2] = {0, 1};
     if (p.n_frames == 0) {                                 // (nothing to run needs nothing: report what one frame takes, never 0 for a good model)
-        const int32_t one[2] = {0, 1};
-        if (hmmr_tracks_plan(one, 1, model->sequence_length, model->fov, max_frames, max_windows, &p)) return 0;
-        return carve_tracks(model, one, 1, p, &c) ? 0 : c.total;
+        off = one, n_tracks = 1;
+        if (hmmr_tracks_plan_as(who, off, n_tracks, model->sequence_length, model->fov, max_frames, max_windows, &p)) return 0;
     }
-    return carve_tracks(model, track_offsets, n_tracks, p, &c) ? 0 : c.total;
+    Carve c;
+    return carve_tracks(model, who, off, n_tracks, p, &c) ? 0 : c.total;
 }
 
-extern "C" int hmmr_predict_tracks(const hmmr_model_t* model, const float* images, const int32_t* track_offsets, int n_tracks, float* rec,
-                                   int64_t ld_rec, const int32_t* field_offsets, int max_frames, int max_windows, void* ws, size_t ws_bytes,
-                                   void* stream) {
-    if (check_model(model, "hmmr_predict_tracks")) return -1;
+int predict(const char* who, const hmmr_model_t* model, const float* images, const int32_t* off, int n_tracks, float* rec, int64_t ld_rec,
+            const int32_t* field_offsets, int max_frames, int max_windows, void* ws, size_t ws_bytes, void* stream) {
+    if (check_model(model, who)) return -1;
     hmmr_tracks_plan_t p;
-    if (hmmr_tracks_plan(track_offsets, n_tracks, model->sequence_length, model->fov, max_frames, max_windows, &p)) return -1;
-    if (check_record(model, field_offsets, ld_rec, "hmmr_predict_tracks")) return -1;
+    if (hmmr_tracks_plan_as(who, off, n_tracks, model->sequence_length, model->fov, max_frames, max_windows, &p)) return -1;
+    if (check_record(model, field_offsets, ld_rec, who)) return -1;
     const int R = model->ief->num_regressors;
     if (p.n_frames == 0) return 0;
-    VIDEO_REQUIRE(images && rec && ws, "hmmr_predict_tracks: null images, rec or ws");
-    VIDEO_REQUIRE(((uintptr_t)ws & 255u) == 0, "hmmr_predict_tracks: ws must be 256-byte aligned");
-    VIDEO_REQUIRE(((uintptr_t)images & 15u) == 0, "hmmr_predict_tracks: images must be 16-byte aligned (hmmr_resnet50_fwd reads them as aligned groups of 4 floats)");
+    VIDEO_REQUIRE(images && rec && ws, "%s: null images, rec or ws", who);
+    VIDEO_REQUIRE(((uintptr_t)ws & 255u) == 0, "%s: ws must be 256-byte aligned", who);
+    VIDEO_REQUIRE(((uintptr_t)images & 15u) == 0, "%s: images must be 16-byte aligned (hmmr_resnet50_fwd reads them as aligned groups of 4 floats)", who);
     Carve c;
-    if (carve_tracks(model, track_offsets, n_tracks, p, &c)) return -1;
-    VIDEO_REQUIRE(ws_bytes >= c.total, "hmmr_predict_tracks: workspace too small (%zu < %zu)", ws_bytes, c.total);
+    if (carve_tracks(model, who, off, n_tracks, p, &c)) return -1;
+    VIDEO_REQUIRE(ws_bytes >= c.total, "%s: workspace too small (%zu < %zu)", who, ws_bytes, c.total);
     if (check_units(model, p.n_frames - (p.resnet_passes - 1) * p.max_frames, p.resnet_passes, p.max_frames)) return -1;
 
     char* base = (char*)ws;
@@ -254,19 +183,47 @@ extern "C" int hmmr_predict_tracks(const hmmr_model_t* model, const float* image
     float* omegas = (float*)(region + c.omegas);
     for (int i = 0; i < p.tail_passes; ++i) {
         TailPass t;
-        if (hmmr_tracks_tail_pass(track_offsets, n_tracks, &p, i, &t.w0, &t.nw, &t.o0, &t.keep)) return -2;      // (carve_tracks walked every pass: cannot fail)
-        if (hmmr_gather_windows_tracks(phi, phi + (size_t)p.n_frames * C, track_offsets, n_tracks, t.w0, t.nw, p.T, p.margin, p.g, C, windows, stream))
-            return -2;
+        if (hmmr_tracks_tail_pass(off, n_tracks, &p, i, &t.w0, &t.nw, &t.o0, &t.keep)) return -2;      // (carve_tracks walked every pass: cannot fail)
+        if (hmmr_gather_windows_tracks(phi, phi + (size_t)p.n_frames * C, off, n_tracks, t.w0, t.nw, p.T, p.margin, p.g, C, windows, stream)) return -2;
         if (model->temporal) {
             if (hmmr_temporal_fwd(model->temporal, windows, t.nw, p.T, strips, region + c.movie_ws, c.movie_bytes, stream)) return -2;
         } else if (hmmr_hallucinator_fwd(model->hallucinator, windows, t.nw * p.T, strips, region + c.movie_ws, c.movie_bytes, stream)) {
             return -2;
         }
-        if (hmmr_keep_rows_tracks(strips, track_offsets, n_tracks, t.w0, t.nw, p.T, p.margin, p.g, C, kept, C, stream)) return -2;
+        if (hmmr_keep_rows_tracks(strips, off, n_tracks, t.w0, t.nw, p.T, p.margin, p.g, C, kept, C, stream)) return -2;
         if (hmmr_ief_fwd(model->ief, kept, t.keep, omegas, region + c.ief_ws, c.ief_bytes, stream)) return -2;
         if (hmmr_smpl_fwd_records(model->smpl, omegas, R, t.keep, rec + (size_t)t.o0 * (size_t)ld_rec, ld_rec, field_offsets,
                                   region + c.smpl_ws, c.smpl_bytes, stream))
             return -2;
     }
     return 0;
+}
+
+}  // namespace
+
+extern "C" size_t hmmr_predict_tracks_workspace_bytes(const hmmr_model_t* model, const int32_t* track_offsets, int n_tracks, int max_frames,
+                                                      int max_windows) {
+    return workspace_bytes("hmmr_predict_tracks_workspace_bytes", model, track_offsets, n_tracks, max_frames, max_windows);
+}
+
+extern "C" int hmmr_predict_tracks(const hmmr_model_t* model, const float* images, const int32_t* track_offsets, int n_tracks, float* rec,
+                                   int64_t ld_rec, const int32_t* field_offsets, int max_frames, int max_windows, void* ws, size_t ws_bytes,
+                                   void* stream) {
+    return predict("hmmr_predict_tracks", model, images, track_offsets, n_tracks, rec, ld_rec, field_offsets, max_frames, max_windows, ws, ws_bytes,
+                   stream);
+}
+
+// A video is one track.  n < 0 is refused here: as an offset it would read "track_offsets must not decrease".
+extern "C" size_t hmmr_predict_video_workspace_bytes(const hmmr_model_t* model, int n, int max_frames, int max_windows) {
+    if (n < 0) { hmmr_set_error("hmmr_predict_video_workspace_bytes: n=%d must not be negative", n); return 0; }
+    const int32_t off[2] = {0, n};
+    return workspace_bytes("hmmr_predict_video_workspace_bytes", model, off, 1, max_frames, max_windows);
+}
+
+extern "C" int hmmr_predict_video(const hmmr_model_t* model, const float* images, int n, float* rec, int64_t ld_rec,
+                                  const int32_t* field_offsets, int max_frames, int max_windows, void* ws, size_t ws_bytes,
+                                  void* stream) {
+    VIDEO_REQUIRE(n >= 0, "hmmr_predict_video: n=%d must not be negative", n);
+    const int32_t off[2] = {0, n};
+    return predict("hmmr_predict_video", model, images, off, 1, rec, ld_rec, field_offsets, max_frames, max_windows, ws, ws_bytes, stream);
 }

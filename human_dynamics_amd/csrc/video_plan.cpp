@@ -11,32 +11,10 @@ namespace {
 inline int ceil_div(int a, int b) { return (int)(((long long)a + b - 1) / b); }
 }  // namespace
 
-extern "C" int hmmr_video_plan(int n, int T, int fov, int max_frames, int max_windows, hmmr_video_plan_t* out) {
-    if (!out) { hmmr_set_error("hmmr_video_plan: null argument"); return -1; }
-    if (fov < 1 || fov % 2 == 0) { hmmr_set_error("hmmr_video_plan: fov=%d must be odd and >= 1", fov); return -1; }
-    const int margin = (fov - 1) / 2;
-    if (T < 1 || (long long)T - 2LL * margin < 1) {
-        hmmr_set_error("hmmr_video_plan: a window of T=%d frames keeps none under fov=%d (g = T - (fov - 1) < 1)", T, fov);
-        return -1;
-    }
-    if (n < 0 || max_frames < 1 || max_windows < 1) {
-        hmmr_set_error("hmmr_video_plan: n=%d must be >= 0, max_frames=%d and max_windows=%d >= 1", n, max_frames, max_windows);
-        return -1;
-    }
-    hmmr_video_plan_t p = {};
-    p.n = n; p.T = T; p.fov = fov;
-    p.margin = margin; p.g = T - 2 * margin;
-    p.n_windows = ceil_div(n, p.g);
-    p.max_frames = max_frames; p.max_windows = max_windows;
-    p.resnet_passes = ceil_div(n, max_frames);
-    p.tail_passes = ceil_div(p.n_windows, max_windows);
-    *out = p;
-    return 0;
-}
-
 // ----------------------------------------------------------------------------------------------------------------------------------
 // Several tracks one after the other along the frame axis (hmmr_predict_tracks): every track has its own zero-image padding, its own
-// window grid and its own kept rows; the windows are numbered globally, track after track (include/hmmr_hip.h: the ragged rule).
+// window grid and its own kept rows; the windows are numbered globally, track after track (include/hmmr_hip.h: the ragged rule).  A
+// video is the one-track case {0, n}, and hmmr_video_plan is that plan under the one-video struct.
 
 // the refusals every entry point that takes track_offsets shares (csrc/windows.hip, csrc/video.cpp); `who` names the caller
 int hmmr_tracks_check_offsets(const char* who, const int32_t* off, int n_tracks) {
@@ -57,29 +35,53 @@ int hmmr_tracks_check_offsets(const char* who, const int32_t* off, int n_tracks)
     return 0;
 }
 
-extern "C" int hmmr_tracks_plan(const int32_t* track_offsets, int n_tracks, int T, int fov, int max_frames, int max_windows,
-                                hmmr_tracks_plan_t* out) {
-    if (!out) { hmmr_set_error("hmmr_tracks_plan: null argument"); return -1; }
-    if (hmmr_tracks_check_offsets("hmmr_tracks_plan", track_offsets, n_tracks)) return -1;
-    if (fov < 1 || fov % 2 == 0) { hmmr_set_error("hmmr_tracks_plan: fov=%d must be odd and >= 1", fov); return -1; }
+namespace {
+// What both plans refuse and compute alike.  off: n_tracks + 1 values that start at 0 and do not decrease (hmmr_tracks_check_offsets,
+// or {0, n} of hmmr_video_plan -- the only caller whose last value may be negative, or INT32_MAX); `who` names the public caller.
+int plan_windows(const char* who, const int32_t* off, int n_tracks, int T, int fov, int max_frames, int max_windows, hmmr_tracks_plan_t* out) {
+    if (fov < 1 || fov % 2 == 0) { hmmr_set_error("%s: fov=%d must be odd and >= 1", who, fov); return -1; }
     const int margin = (fov - 1) / 2;
     if (T < 1 || (long long)T - 2LL * margin < 1) {
-        hmmr_set_error("hmmr_tracks_plan: a window of T=%d frames keeps none under fov=%d (g = T - (fov - 1) < 1)", T, fov);
+        hmmr_set_error("%s: a window of T=%d frames keeps none under fov=%d (g = T - (fov - 1) < 1)", who, T, fov);
         return -1;
     }
-    if (max_frames < 1 || max_windows < 1) {
-        hmmr_set_error("hmmr_tracks_plan: max_frames=%d and max_windows=%d must be >= 1", max_frames, max_windows);
+    if (off[n_tracks] < 0 || max_frames < 1 || max_windows < 1) {
+        hmmr_set_error("%s: n=%d must be >= 0, max_frames=%d and max_windows=%d >= 1", who, (int)off[n_tracks], max_frames, max_windows);
         return -1;
     }
     hmmr_tracks_plan_t p = {};
     p.n_tracks = n_tracks; p.T = T; p.fov = fov;
     p.margin = margin; p.g = T - 2 * margin;
-    p.n_frames = track_offsets[n_tracks];
-    for (int k = 0; k < n_tracks; ++k) p.n_windows += ceil_div(track_offsets[k + 1] - track_offsets[k], p.g);     // <= n_frames: no overflow
+    p.n_frames = off[n_tracks];
+    for (int k = 0; k < n_tracks; ++k) p.n_windows += ceil_div(off[k + 1] - off[k], p.g);     // <= n_frames: no overflow
     p.max_frames = max_frames; p.max_windows = max_windows;
     p.resnet_passes = ceil_div(p.n_frames, max_frames);
     p.tail_passes = ceil_div(p.n_windows, max_windows);
     *out = p;
+    return 0;
+}
+}  // namespace
+
+// hmmr_tracks_plan under the name of the entry point that plans (csrc/video.cpp: its refusals name the call that was made)
+int hmmr_tracks_plan_as(const char* who, const int32_t* track_offsets, int n_tracks, int T, int fov, int max_frames, int max_windows,
+                        hmmr_tracks_plan_t* out) {
+    if (hmmr_tracks_check_offsets(who, track_offsets, n_tracks)) return -1;
+    return plan_windows(who, track_offsets, n_tracks, T, fov, max_frames, max_windows, out);
+}
+
+extern "C" int hmmr_tracks_plan(const int32_t* track_offsets, int n_tracks, int T, int fov, int max_frames, int max_windows,
+                                hmmr_tracks_plan_t* out) {
+    if (!out) { hmmr_set_error("hmmr_tracks_plan: null argument"); return -1; }
+    return hmmr_tracks_plan_as("hmmr_tracks_plan", track_offsets, n_tracks, T, fov, max_frames, max_windows, out);
+}
+
+// one video: no offsets check -- n = INT32_MAX is a plan (its ceil_div is 64-bit), though no call can run it
+extern "C" int hmmr_video_plan(int n, int T, int fov, int max_frames, int max_windows, hmmr_video_plan_t* out) {
+    if (!out) { hmmr_set_error("hmmr_video_plan: null argument"); return -1; }
+    const int32_t off[2] = {0, n};
+    hmmr_tracks_plan_t t;
+    if (plan_windows("hmmr_video_plan", off, 1, T, fov, max_frames, max_windows, &t)) return -1;
+    *out = {n, T, fov, t.margin, t.g, t.n_windows, max_frames, max_windows, t.resnet_passes, t.tail_passes};      // (the struct's order)
     return 0;
 }
 

@@ -448,37 +448,46 @@ class Tester(object):
         model.sequence_length, model.fov = self.sequence_length, self.fov
         return model
 
+    def _native_records(self, frames, who, max_frames, max_windows):
+        """ONE call of the library over device frames [n,224,224,3] (None when there is none): hmmr_predict_video when `who` is the frame
+        count n, hmmr_predict_tracks when it is the int32 array of n_tracks + 1 offsets.  Returns (rec [n, rec_len] on the device, the
+        layout of record_layout()), synchronised -- the saturation guard reads the flags this call raised."""
+        import ctypes as C
+        from ..engine import _Workspace
+        eng = self.engine
+        model = self.native_model()
+        if isinstance(who, np.ndarray):
+            name, n, args = "hmmr_predict_tracks", int(who[-1]), (who.ctypes.data_as(C.POINTER(C.c_int32)), len(who) - 1)
+        else:
+            name, n, args = "hmmr_predict_video", int(who), (int(who),)
+        R = eng.iw.num_regressors
+        offs, ld_rec = (C.c_int32 * (R * 7))(), C.c_int64(0)
+        L.check(eng.lib.hmmr_record_layout(eng.num_kps, eng.num_verts, R, offs, C.byref(ld_rec)), "hmmr_record_layout")
+        layout, rec_len = self.record_layout()
+        assert rec_len == ld_rec.value, (rec_len, ld_rec.value)
+        rec = torch.empty((n, rec_len), dtype=torch.float32, device=eng.device)
+        nbytes = getattr(eng.lib, name + "_workspace_bytes")(C.byref(model), *args, max_frames, max_windows)
+        if not nbytes:
+            L.check(-1, name + "_workspace_bytes")
+        ws = eng._ws.setdefault("video", _Workspace(eng.device)).get(nbytes)
+        L.check(getattr(eng.lib, name)(C.byref(model), frames.data_ptr() if n else None, *args, rec.data_ptr() if n else None, rec_len, offs,
+                                       max_frames, max_windows, ws.data_ptr(), nbytes, eng._stream()), name)
+        torch.cuda.synchronize(eng.device)
+        return rec, layout
+
     def predict_all_images_native(self, all_images, want=None, max_frames=MAX_DEVICE_FRAMES, max_windows=MAX_TAIL_WINDOWS):
         """`predict_all_images` through the library's own whole-video call (hmmr_predict_video, include/hmmr_hip.h): the ResNet
         passes, the window gather, f_movie, the kept rows, IEF and SMPL are queued by ONE C call on the engine's already-packed
         structs -- what a caller without Python and torch runs (tests/c_abi/predict_video.c).  Same dict, same bytes.
         all_images: [N,224,224,3] float32 in [-1,1], host or device.  max_frames / max_windows: frames per ResNet pass and
         windows per tail pass; they bound the workspace and change no bit."""
-        import ctypes as C
         from ..dist import unpack_outputs
-        from ..engine import _Workspace
-        max_frames, max_windows = int(max_frames), int(max_windows)
 
         def run():
-            eng = self.engine
-            model = self.native_model()
-            frames = eng.to_device(all_images)
+            frames = self.engine.to_device(all_images)
             n = frames.shape[0]
             assert n == 0 or tuple(frames.shape[1:]) == (224, 224, 3), frames.shape
-            R = eng.iw.num_regressors
-            offs, ld_rec = (C.c_int32 * (R * 7))(), C.c_int64(0)
-            L.check(eng.lib.hmmr_record_layout(eng.num_kps, eng.num_verts, R, offs, C.byref(ld_rec)), "hmmr_record_layout")
-            layout, rec_len = self.record_layout()
-            assert rec_len == ld_rec.value, (rec_len, ld_rec.value)
-            rec = torch.empty((n, rec_len), dtype=torch.float32, device=eng.device)
-            nbytes = eng.lib.hmmr_predict_video_workspace_bytes(C.byref(model), n, max_frames, max_windows)
-            if not nbytes:
-                L.check(-1, "hmmr_predict_video_workspace_bytes")
-            ws = eng._ws.setdefault("video", _Workspace(eng.device)).get(nbytes)
-            L.check(eng.lib.hmmr_predict_video(C.byref(model), frames.data_ptr() if n else None, n, rec.data_ptr() if n else None,
-                                               rec_len, offs, max_frames, max_windows, ws.data_ptr(), nbytes, eng._stream()),
-                    "hmmr_predict_video")
-            torch.cuda.synchronize(eng.device)
+            rec, layout = self._native_records(frames, n, int(max_frames), int(max_windows))
             return {k: v.float().cpu().numpy() for k, v in unpack_outputs(rec, layout).items() if want is None or k in want}
         return self._guard_saturation(run)
 
@@ -498,11 +507,8 @@ class Tester(object):
         max_frames / max_windows: frames per ResNet pass and windows per tail pass; they bound the workspace and change no bit.
         The call runs inside the saturation guard: if any split-fp16 store of the batch clamps a value, the WHOLE batch is repeated
         with fp32 operands (and the Tester keeps them); the equality with the per-track loop holds for calls that raise no flag."""
-        import ctypes as C
         from ..dist import unpack_outputs
-        from ..engine import _Workspace
         tracks = list(tracks)
-        max_frames, max_windows = int(max_frames), int(max_windows)
         for k, trk in enumerate(tracks):
             if (trk.dtype == torch.uint8) if isinstance(trk, torch.Tensor) else (np.asarray(trk).dtype == np.uint8):
                 raise ValueError("track %d: uint8 input goes through the streamed path (predict_videos / predict_all_images, stream=True)" % k)
@@ -510,29 +516,12 @@ class Tester(object):
                 raise ValueError("track %d: frames of shape %s, need [N,224,224,3]" % (k, tuple(trk.shape)))
 
         def run():
-            eng = self.engine
-            model = self.native_model()
-            parts = [eng.to_device(trk).reshape(-1, 224, 224, 3) for trk in tracks if len(trk)]
+            parts = [self.engine.to_device(trk).reshape(-1, 224, 224, 3) for trk in tracks if len(trk)]
             offsets = np.zeros(len(tracks) + 1, np.int32)
             np.cumsum([len(trk) for trk in tracks], out=offsets[1:])
-            n = int(offsets[-1])
-            off_p = offsets.ctypes.data_as(C.POINTER(C.c_int32))
             frames = parts[0] if len(parts) == 1 else torch.cat(parts, dim=0) if parts else None
-            R = eng.iw.num_regressors
-            offs, ld_rec = (C.c_int32 * (R * 7))(), C.c_int64(0)
-            L.check(eng.lib.hmmr_record_layout(eng.num_kps, eng.num_verts, R, offs, C.byref(ld_rec)), "hmmr_record_layout")
-            layout, rec_len = self.record_layout()
-            assert rec_len == ld_rec.value, (rec_len, ld_rec.value)
-            rec = torch.empty((n, rec_len), dtype=torch.float32, device=eng.device)
-            nbytes = eng.lib.hmmr_predict_tracks_workspace_bytes(C.byref(model), off_p, len(tracks), max_frames, max_windows)
-            if not nbytes:
-                L.check(-1, "hmmr_predict_tracks_workspace_bytes")
-            ws = eng._ws.setdefault("video", _Workspace(eng.device)).get(nbytes)
-            L.check(eng.lib.hmmr_predict_tracks(C.byref(model), frames.data_ptr() if n else None, off_p, len(tracks), rec.data_ptr() if n else None,
-                                                rec_len, offs, max_frames, max_windows, ws.data_ptr(), nbytes, eng._stream()),
-                    "hmmr_predict_tracks")
+            rec, layout = self._native_records(frames, offsets, int(max_frames), int(max_windows))
             views = [rec[int(offsets[k]):int(offsets[k + 1])] for k in range(len(tracks))]
-            torch.cuda.synchronize(eng.device)          # (also for records: the guard reads the flags this call raised)
             if records:
                 return views, layout
             return [{k: v.float().cpu().numpy() for k, v in unpack_outputs(view, layout).items() if want is None or k in want} for view in views]

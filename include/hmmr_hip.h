@@ -973,7 +973,12 @@ int hmmr_record_layout(int num_kps, int num_verts, int num_containers, int32_t* 
  *   out [n_windows][T][c], windows w0 .. w0 + n_windows - 1.
  * hmmr_keep_rows (tester.py:306-311): strips [n_windows][T][c] of the same windows -> for 0 <= j < g, slot margin + j of
  *   window w is frame f = w g + j and goes to out + (f - w0 g) ld_out if f < n_total (ld_out >= c, ld_out % 4 == 0); rows
- *   with f >= n_total and the columns c .. ld_out - 1 are not touched. */
+ *   with f >= n_total and the columns c .. ld_out - 1 are not touched.
+ * Each is the one-track case {0, n} of its _tracks sibling below, run by the same kernel, and accepts more than the sibling
+ * does: hmmr_gather_windows takes any w0, n_windows >= 0, also windows past ceil(n / g) (the reference runs count *
+ * batch_size of them; their slots from frame n on hold phi_zero), where the sibling refuses a range that leaves the
+ * numbering; hmmr_keep_rows clips its windows' rows at n_total and returns 0 without a launch when none is left (w0 g >=
+ * n_total), where the sibling refuses. */
 int hmmr_gather_windows(const float* phi, int n, const float* phi_zero, int w0, int n_windows, int T, int margin, int g,
                         int c, float* out, void* stream);
 int hmmr_keep_rows(const float* strips, int w0, int n_windows, int T, int margin, int g, int c, int n_total, float* out,
@@ -1002,7 +1007,11 @@ typedef struct {
  * Per-frame encoder, per-window tail, split_k never chosen from the batch: the records do not depend on max_frames /
  * max_windows, bit for bit.  The call reads no run flags: read hmmr_run_flags where the records are read.
  * The workspace (0: bad model or plan) holds phi and, one after the other on the stream, the ResNet workspace of
- * min(n, max_frames) + 1 frames and the tail's buffers for min(n_windows, max_windows) windows; it never shrinks as n grows. */
+ * min(n, max_frames) + 1 frames and the tail's buffers for min(n_windows, max_windows) windows; it never shrinks as n grows.
+ * The call is hmmr_predict_tracks (below) with one track, track_offsets = {0, n}: the same driver, the same workspace, the
+ * same refusals under this call's name.  Beyond the sibling it refuses n < 0 itself; like the sibling, and unlike
+ * hmmr_video_plan, it refuses n = INT32_MAX (row n, the zero image's, would not be a 32-bit row number), in the call and in
+ * the query (0). */
 size_t hmmr_predict_video_workspace_bytes(const hmmr_model_t* model, int n, int max_frames, int max_windows);
 int hmmr_predict_video(const hmmr_model_t* model, const float* images, int n, float* rec, int64_t ld_rec,
                        const int32_t* field_offsets, int max_frames, int max_windows, void* ws, size_t ws_bytes,

@@ -1,7 +1,11 @@
 """Every tracked person through one C call (include/hmmr_hip.h: hmmr_predict_tracks, Tester.predict_tracks): the two ragged copies alone
 (csrc/windows.hip) against the NumPy rule of tests/tracks_rule.py and against the one-video copies run on every track's slice, the call
 against the per-track route byte for byte -- one pass and several, both f_movie forms -- its refusals, and the Python layer up to the
-scene view."""
+scene view.
+
+The one-video copies are the ragged kernels launched with a one-track table, so the comparison with them on every track's slice
+(test_gather_follows_the_ragged_rule) checks the table the one-video entry builds, not a second implementation.  Each form keeps a pin
+of its own: the one-video form tests/golden/reference_windows.npz (tests/test_gpu_video_call.py), the ragged form tests/tracks_rule.py."""
 import ctypes as C
 
 import numpy as np
@@ -246,6 +250,34 @@ def test_one_track_gives_the_one_video_call_s_record_buffer(testers, frames24, g
     for lengths in ([], [0, 0]):
         off0 = offsets(lengths)
         assert lib.hmmr_predict_tracks(C.byref(model), None, _p(off0), len(lengths), None, rec_len, offs, 1024, 128, None, 0, _stream(gpu_device)) == 0
+
+
+def test_the_two_public_entries_agree(testers, reference, frames24, gpu_device):
+    """a video is the one-track case: for the 9 frames of CUTS[1], several ResNet and tail passes, hmmr_predict_video and hmmr_predict_tracks
+    with {0, 9} ask for the same workspace and write the same bytes, those of the per-track route"""
+    import torch
+    from human_dynamics_amd.dist import unpack_outputs
+    t, lib = testers("f32"), L.load()
+    a, b = CUTS[1]
+    N, mf, mw = b - a, 8, 1
+    assert N == 9
+    frames = torch.from_numpy(frames24[a:b]).to(gpu_device)
+    layout, rec_len, offs = _layout_args(t, lib)
+    model = t.native_model()
+    off = offsets([N])
+    nbytes = lib.hmmr_predict_video_workspace_bytes(C.byref(model), N, mf, mw)
+    assert nbytes == lib.hmmr_predict_tracks_workspace_bytes(C.byref(model), _p(off), 1, mf, mw) > 0
+    ws = torch.empty(nbytes, dtype=torch.uint8, device=gpu_device)
+    one = torch.full((N, rec_len), SENTINEL, dtype=torch.float32, device=gpu_device)
+    many = torch.full((N, rec_len), SENTINEL, dtype=torch.float32, device=gpu_device)
+    L.check(lib.hmmr_predict_video(C.byref(model), frames.data_ptr(), N, one.data_ptr(), rec_len, offs, mf, mw, ws.data_ptr(), nbytes,
+                                   _stream(gpu_device)), "hmmr_predict_video")
+    L.check(lib.hmmr_predict_tracks(C.byref(model), frames.data_ptr(), _p(off), 1, many.data_ptr(), rec_len, offs, mf, mw, ws.data_ptr(), nbytes,
+                                    _stream(gpu_device)), "hmmr_predict_tracks")
+    torch.cuda.synchronize(gpu_device)
+    assert torch.equal(one.view(torch.int32), many.view(torch.int32))
+    for rec in (one, many):
+        _same_bytes({k: v.cpu().numpy() for k, v in unpack_outputs(rec, layout).items()}, reference("f32", 1))
 
 
 def test_tracks_call_in_hal_mode_equals_the_per_track_route(smpl_consts, gpu_device):

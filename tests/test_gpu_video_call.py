@@ -54,9 +54,11 @@ def _gather(lib, phi, zero, w0, nw, dev):
 def test_gather_feeds_what_the_reference_fed(gpu_device, windows, N, B, c):
     lib = L.load()
     phi, zero = _phi(N, c, gpu_device)
-    nw = -(-N // G)
-    got = _gather(lib, phi, zero, 0, nw, gpu_device)
-    fed = windows["fed_n%d_b%d" % (N, B)][:nw]                                           # frame numbers from 1; -1 = the zero image
+    fed = windows["fed_n%d_b%d" % (N, B)]                                                # frame numbers from 1; -1 = the zero image
+    assert fed.shape[0] == {1: 8, 24: 4, 64: 8, 65: 16, 100: 15, 256: 32}[N] >= -(-N // G)
+    # every window the reference ran, count * batch_size of them: those past ceil(N / G) keep no frame, but the early slots of the first
+    # one still hold real frames -- the one-video gather takes any window range, not only the numbering of its single track
+    got = _gather(lib, phi, zero, 0, fed.shape[0], gpu_device)
     col = np.arange(c, dtype=np.float64)
     want = np.where(fed[..., None] > 0, 4096.0 * (fed[..., None] - 1) + col, -1.0 - col).astype(np.float32)
     assert np.array_equal(got, want)
@@ -104,6 +106,15 @@ def test_keep_writes_the_centre_rows_and_nothing_else(gpu_device, N, c):
         _keep(lib, strips, w0, nw - w0, N, two, w0 * G, gpu_device)
         torch.cuda.synchronize(gpu_device)
         assert np.array_equal(two.cpu().numpy(), got)
+    if N == 9:      # two windows more than hold a kept frame: the copy clips at n_total and writes rows 0 .. 8 only ...
+        more = torch.full_like(out, SENTINEL)
+        L.check(lib.hmmr_keep_rows(strips.data_ptr(), 0, 4, T, MARGIN, G, c, N, more.data_ptr(), ld, _stream(gpu_device)), "hmmr_keep_rows")
+        torch.cuda.synchronize(gpu_device)
+        assert np.array_equal(more.cpu().numpy(), got)
+        # ... and windows that hold none are no error: 0, and nothing is written
+        assert lib.hmmr_keep_rows(strips.data_ptr(), 2, 2, T, MARGIN, G, c, N, more[2 * G:].data_ptr(), ld, _stream(gpu_device)) == 0
+        torch.cuda.synchronize(gpu_device)
+        assert np.array_equal(more.cpu().numpy(), got)
 
 
 # ------------------------------------------------------------------------- the whole call
