@@ -182,6 +182,8 @@ RENDER_BG_COLOR, RENDER_BG_FLOAT, RENDER_BG_FRAME = 0, 1, 2
 # hmmr_track_* (csrc/track.hip): limits, the gap scan's step, the status bits of hmmr_track_crop_geom
 TRACK_MAX_KPS, TRACK_MAX_KERNEL, TRACK_MAX_RADIUS, TRACK_MAX_ROWS, TRACK_TILE = 64, 31, 64, 1 << 27, 256
 TRACK_EMPTY, TRACK_BEFORE_ORIGIN, TRACK_CLIPPED, TRACK_NOT_FINITE = 1, 2, 4, 8
+# hmmr_video_bbox (csrc/person_view.hip): the status bits of a track's box
+BBOX_EMPTY, BBOX_NOT_FINITE, BBOX_DEGENERATE, BBOX_BEYOND_START = 1, 2, 4, 8
 
 
 class RenderDesc(C.Structure):
@@ -291,6 +293,8 @@ SIGNATURES = {
     "hmmr_render_mesh": (C.c_int, [C.POINTER(RenderDesc), _vp]),
     "hmmr_render_scene_workspace_bytes": (C.c_size_t, [C.c_int, C.c_int, C.c_int, C.c_int]),
     "hmmr_render_scene": (C.c_int, [C.POINTER(SceneDesc), _vp]),
+    "hmmr_video_bbox": (C.c_int, [_fp, C.c_longlong, _fp, C.c_longlong, C.c_int, _fp, C.c_double, C.POINTER(C.c_int32), C.c_int, C.c_int, C.c_int,
+                                  C.c_double, _ip, _fp, _ip, _vp]),
     "hmmr_skeleton_radius": (C.c_int, [C.c_int, C.c_int]),
     "hmmr_draw_skeleton": (C.c_int, [C.POINTER(SkeletonDesc), _vp]),
     "hmmr_collage_width": (C.c_int, [C.c_int, C.c_int, C.c_int]),

@@ -23,6 +23,13 @@ measured; no text is drawn.
 
 is not the reference's (it renders one track per video): all tracks of a video over each original frame, one PNG per frame
 and one mp4 (util/render/video.render_scene, include/hmmr_hip.h: hmmr_render_scene).
+
+    render_person_clips(output_path, tracks, frames, faces=...)
+
+is the reference's person-centred view (compute_video_bbox + visualize_mesh_og, src/util/render/nmr_renderer.py) as a driver,
+which the reference does not have: one folder of PNGs and one mp4 per tracked person, cropped to the box that holds the
+person over the whole video, the mesh seen from several angles side by side (util/render/video.render_person_clips,
+include/hmmr_hip.h: hmmr_video_bbox).
 """
 from __future__ import annotations
 
@@ -294,3 +301,79 @@ def render_tracks(output_path, tracks, frames, faces=None, face_path='src/tf_smp
     else:
         result["note"] = "ffmpeg failed: the PNG frames are left in %s" % output_path
     return result
+
+
+def render_person_clips(output_path, tracks, frames, faces=None, face_path='src/tf_smpl/smpl_faces.npy', chunk=64, degs=(0, 90), margin=10,
+                        max_img_size=300, background=True, colors=None, device=None):
+    """One person-centred clip per track of a video:
+
+        output_path/track%02d/frame%06d.png   the views of `degs` side by side, each (h', w') of the track's video-level box
+        output_path/track%02d.mp4             where an ffmpeg is installed
+
+    tracks: per track (records_or_dict, layout, (start, end), image_og_params), as util/render/video.render_person_clips takes
+    them; frames: uint8 [F,H,W,3], host or device.  The boxes and the cameras relative to them come from ONE hmmr_video_bbox call
+    over the whole tracks (a box is a property of the whole video); each track is then rendered `chunk` frames at a time and
+    comes to the host as finished uint8 frames.  Frame j of a track's folder is frame start + j of the video.
+    degs / margin / max_img_size / background / colors: as video.render_person_clips (the deg == 0 view over the frames' window
+    is this project's addition; the reference renders on white).  A track that cannot be rendered (an empty or non-finite
+    track, a box without area or beyond the rasteriser's sizes) is named in a warning and in its entry, and skipped.
+    Returns a list with one dict per track: 'frames' (the folder, None for a skipped track), 'n_frames' written, 'bbox',
+    'status', 'size', and `video`: the mp4 path, or None with `note` saying that the mp4 exists already ("Video already
+    exists!": nothing is rendered for that track), that no ffmpeg was found (or that it failed) and the PNG frames were left
+    in place, or why the track was skipped."""
+    import warnings
+    from PIL import Image
+    from ..util.render import person_view, video
+    from ..util.render.nmr_renderer import load_faces
+    from ..util.render.raster import MeshFaces, scene_color
+    if not os.path.exists(output_path):
+        os.mkdir(output_path)
+    mesh_faces = faces if isinstance(faces, MeshFaces) else MeshFaces(faces if faces is not None else load_faces(face_path))
+    if device is None:
+        r0 = tracks[0][0]
+        r0 = r0['cams'] if isinstance(r0, dict) else r0
+        device = r0.device if torch.is_tensor(r0) and r0.device.type == "cuda" else torch.device("cuda", torch.cuda.current_device())
+    frame_hw = tuple(frames.shape[1:3])
+    video.check_track_ranges(tracks, len(frames))
+    bbox, crops, status = video.video_bboxes(tracks, frame_hw, margin, device=device)
+    results = []
+    for t, (records, layout, (start, end), params) in enumerate(tracks):
+        h, w, S = person_view.clip_size(bbox[t], max_img_size)
+        folder, vid_path = os.path.join(output_path, 'track%02d' % t), os.path.join(output_path, 'track%02d.mp4' % t)
+        res = {"frames": None, "n_frames": 0, "bbox": [int(x) for x in bbox[t]], "status": int(status[t]), "size": (h, w, S), "video": None,
+               "note": None}
+        results.append(res)
+        why = video.clip_skip_reason(bbox[t], int(status[t]), (h, w, S))
+        if why:
+            res["note"] = "not rendered: %s" % why
+            warnings.warn("render_person_clips: track %d is not rendered (%s, box %s)" % (t, why, res["bbox"]))
+            continue
+        if os.path.exists(vid_path):
+            print('Video already exists!')
+            res["note"] = "%s exists already" % vid_path
+            continue
+        if not os.path.exists(folder):
+            os.mkdir(folder)
+        res["frames"] = folder
+        for a in range(0, end - start, chunk):
+            b = min(a + chunk, end - start)
+            rec = {k: records[k][a:b] for k in ('cams', 'verts')} if isinstance(records, dict) else records[a:b]
+            _, verts = video._cams_verts(rec, layout, device)
+            fr = None
+            if background:
+                fr = frames[start + a:start + b]
+                fr = (fr if torch.is_tensor(fr) else torch.from_numpy(np.ascontiguousarray(fr))).to(device)
+            views = video.person_clip_views(verts, crops[t][a:b], mesh_faces, bbox[t], (h, w, S), scene_color(t, colors), degs, fr)
+            panels = [views[deg] for deg in degs]
+            side = torch.cat(panels, dim=2).cpu().numpy()
+            for j in range(a, b):
+                Image.fromarray(side[j - a]).save(os.path.join(folder, 'frame{:06d}.png'.format(j)))
+                res["n_frames"] += 1
+        made = make_video(vid_path, folder)
+        if made is None:
+            res["note"] = "no ffmpeg on PATH: the PNG frames are left in %s" % folder
+        elif made:
+            res["video"] = vid_path
+        else:
+            res["note"] = "ffmpeg failed: the PNG frames are left in %s" % folder
+    return results

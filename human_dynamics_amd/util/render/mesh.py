@@ -30,10 +30,10 @@ def latlong_sphere(n_lon=84, n_rings=82):
     return verts, np.asarray(faces, np.int32)
 
 
-def deformed_sphere(seed=0, scale=(0.35, 0.8, 0.25)):
+def deformed_sphere(seed=0, scale=(0.35, 0.8, 0.25), n_lon=84, n_rings=82):
     """The SMPL-sized sphere smoothly deformed into a person-like ellipsoid with low-frequency bumps (metres-ish units,
-    like SMPL's vertices)."""
-    v, f = latlong_sphere()
+    like SMPL's vertices).  n_lon, n_rings: latlong_sphere's (14, 12: 170 vertices, for tests that need a mesh, not its size)."""
+    v, f = latlong_sphere(n_lon, n_rings)
     rng = np.random.default_rng(seed)
     a = rng.uniform(0.05, 0.15, 3)
     k = rng.integers(1, 4, 3)

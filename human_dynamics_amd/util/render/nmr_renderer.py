@@ -6,7 +6,9 @@ panels (they set `.renderer.image_size` and call `__call__` / `rotated`).  The m
 `visualize_img_orig` below are the reference's functions of those names (:265-419) without cv2: the skeleton comes from
 util/render/collage.draw_skeleton, whose draw list is the reference's and whose primitives follow the integer rules of
 include/hmmr_hip.h -- agreement with OpenCV's circles and lines at primitive boundaries has not been measured -- and
-`draw_text` (cv2.putText) is not provided: they take `no_text=True` only.  Inputs may be numpy arrays or device tensors; results
+`draw_text` (cv2.putText) is not provided: they take `no_text=True` only.  `compute_video_bbox` and `visualize_mesh_og`
+(:519-634, :422-488) are the reference's person-centred view: the box of a person over the whole video, the cameras relative to it
+(one hmmr_video_bbox launch) and the mesh, optionally turned, in a square of the box's size.  Inputs may be numpy arrays or device tensors; results
 are what the reference returns (uint8 numpy: [S,S,3], [B,S,S,3], RGBA [S,S,4], or the silhouette), or the same data as
 device tensors with `on_device=True`.  Only t_size = 1 textures (one colour per face) are supported.
 """
@@ -18,6 +20,8 @@ import torch
 from ... import _lib as L
 from ...tf_smpl.batch_smpl import _SmplUnpickler
 from .collage import draw_skeleton
+from .handoff import orig_image_geometry
+from .person_view import clip_size, proc_rows, video_bbox
 from .raster import COLORS, MeshFaces, render_mesh, rodrigues
 
 colors = COLORS
@@ -258,4 +262,64 @@ def visualize_img_orig(cam, kp_pred, vert, renderer, start_pt, scale, proc_img_s
                          mesh_color=mesh_color, pad_vals=pad_vals, no_text=no_text)
 
 
-__all__ = ["VisRenderer", "colors", "load_faces", "visualize_img", "visualize_img_orig", "make_square", "remove_pads"]
+def _image_hw(im_path):
+    from PIL import Image
+    with Image.open(im_path) as im:
+        return im.size[1], im.size[0]
+
+
+def compute_video_bbox(cams, kps, proc_infos, margin=10, img_shape=None, status=False, device=None):
+    """The reference's function of this name (:519-634) in one hmmr_video_bbox launch: the box [ymin, ymax, xmin, xmax] that
+    holds the person of cams [N,3] / kps [N,K,2] (host arrays, device tensors, or lists of N per-frame arrays or tensors as the
+    reference takes them; crop coordinates in [-1, 1]) over the whole video, and the N cameras relative to it.  proc_infos: process_image's dicts (scale, start_pt, im_shape).
+    img_shape=(h, w) stands for the reference's imread(proc_infos[0]['im_path']); without it that file's size is read with PIL.
+    -> (bbox int array [4], list of N float32 cameras [3]); with status=True also the HMMR_BBOX_* word (_lib.BBOX_*): where the
+    reference prints 'crop is more than start pt..?' and stops in a debugger, BEYOND_START is set and the results are those it
+    computes when continued."""
+    if img_shape is None:
+        img_shape = _image_hw(proc_infos[0]['im_path'])
+    if device is None:
+        first = [x if torch.is_tensor(x) or not len(x) else x[0] for x in (cams, kps)]
+        device = next((x.device for x in first if torch.is_tensor(x) and x.device.type == "cuda"),
+                      torch.device("cuda", torch.cuda.current_device()))
+
+    def up(x):                                         # an array, a tensor, or the reference's list of per-frame arrays / tensors
+        if not torch.is_tensor(x):
+            x = torch.stack(list(x)) if len(x) and torch.is_tensor(x[0]) else torch.as_tensor(np.asarray(x, np.float32))
+        return x.to(device, torch.float32)
+
+    c, k = up(cams), up(kps)
+    n = c.shape[0]
+    c, k = c.reshape(n, -1).contiguous(), k.reshape(n, -1, k.shape[-1])[:, :, :2].reshape(n, -1).contiguous()
+    proc = torch.as_tensor(proc_rows(proc_infos), device=device)
+    bbox, crop, st = video_bbox(c, k, k.shape[1] // 2, proc, [0, n], img_shape, margin, proc_size=float(proc_infos[0]['im_shape'][0]))
+    bbox_h = bbox[0].cpu().numpy().astype(int)
+    new_cams = list(crop.cpu().numpy())
+    return (bbox_h, new_cams, int(st[0])) if status else (bbox_h, new_cams)
+
+
+def visualize_mesh_og(cam, vert, renderer, start_pt, scale, proc_img_shape, im_path=None, img=None, deg=0, mesh_color='blue',
+                      max_img_size=300, pad=50, crop_cam=None, bbox=None):
+    """The reference's function of this name (:422-488): the mesh, turned by `deg` about y, in the space of the original image
+    (bbox None: the camera moves from the crop to the image as in visualize_img_orig) or of the video-level box
+    (bbox, crop_cam: compute_video_bbox's).  The image (img [H,W,...], or im_path, whose size is read with PIL) only decides the
+    size, as in the reference: the window of the box or the whole image, down-scaled to max_img_size and squared.  Sets
+    renderer.renderer.image_size and returns renderer.rotated(...)."""
+    hw = tuple(img.shape[:2]) if img is not None else _image_hw(im_path)
+    if bbox is not None:
+        assert crop_cam is not None
+        rows, cols = range(hw[0])[int(bbox[0]):int(bbox[1])], range(hw[1])[int(bbox[2]):int(bbox[3])]      # img[ymin:ymax, xmin:xmax], clipped as a slice is
+        renderer.renderer.image_size = clip_size([0, len(rows), 0, len(cols)], max_img_size)[2]
+        return renderer.rotated(vert, deg, cam=crop_cam, color_name=mesh_color)
+    undo_scale, sx, sy, proc, img_size = orig_image_geometry({"scale": scale, "start_pt": start_pt, "im_shape": proc_img_shape}, hw, max_img_size)
+    renderer.renderer.image_size = int(img_size)
+    cam = np.asarray(_host(cam), np.float64)
+    cam_crop = np.hstack([proc * cam[0] * 0.5, cam[1:] + (2. / cam[0]) * 0.5])
+    cam_orig = np.hstack([cam_crop[0] * undo_scale, cam_crop[1:] + (np.array([sx, sy]) - proc) / cam_crop[0]])
+    k = 2. / int(img_size)
+    new_cam = np.hstack([cam_orig[0] * k, cam_orig[1:] - (1 / (k * cam_orig[0]))]).astype(np.float32)
+    return renderer.rotated(vert, deg, cam=new_cam, color_name=mesh_color)
+
+
+__all__ = ["VisRenderer", "colors", "load_faces", "visualize_img", "visualize_img_orig", "make_square", "remove_pads",
+           "compute_video_bbox", "visualize_mesh_og"]

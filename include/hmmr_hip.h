@@ -779,6 +779,46 @@ size_t hmmr_render_scene_workspace_bytes(int n_frames, int n_tracks, int nv, int
 int hmmr_render_scene(const hmmr_scene_desc_t* d, void* stream);
 
 /* ------------------------------------------------------------------------- *
+ * The person-centred view (csrc/person_view.hip; additive to ABI 19): compute_video_bbox of
+ * src/util/render/nmr_renderer.py (:519-634) for any number of person tracks in one call -- the one box that holds a person
+ * over the whole track, and every frame's camera re-expressed relative to that box, ready for hmmr_render_mesh at size S
+ * (visualize_mesh_og's crop branch, :440-464).
+ *
+ * cams [N][>= 3] and kps [N][>= 2k] (k (x, y) pairs in the [-1, 1] coordinates of the crop) are fp32 rows read in place
+ * (ld_cam / ld_kps floats apart, e.g. inside the packed per-frame records); proc [N][3] = {scale, start_x, start_y} of
+ * process_image in fp64; proc_size = im_shape[0].  Track t owns rows [offsets[t], offsets[t + 1]); `offsets` is HOST memory,
+ * as for the track front end, and goes to the kernel by value.  One workgroup per track, no atomics, no workspace, nothing
+ * allocated or waited for: the same bits every run, and a track's result does not depend on its neighbours.
+ *
+ * fp64 on the fp32 inputs, every operation rounded by itself (no contraction), in the reference's order.  Per frame:
+ *   undo = 1 / scale;   p = ((kp + 1) * 0.5) * proc_size;   q = ((p + start) - proc_size) * undo
+ *   ymin = max(0, min_k q.y - margin)   ymax = min(img_h - 1, max_k q.y + margin)   xmin, xmax likewise with img_w
+ * per track: bbox = {min ymin, max ymax, min xmin, max xmax} over its frames, each cast to int32 toward zero (astype(np.int));
+ *   off = (xmin, ymin);   S = max(ymax - ymin, xmax - xmin)
+ * per frame again:
+ *   start' = start - off * scale
+ *   c0 = (proc_size * cam[0]) * 0.5;   c12 = cam[1:] + (2 / cam[0]) * 0.5
+ *   o0 = c0 * undo;                    o12 = c12 + (start' - proc_size) / c0
+ *   cams_crop = {o0 * (2 / S), o12 - 1 / ((2 / S) * o0)}, rounded once to fp32.
+ * status [n_tracks]: HMMR_BBOX_* bits.  A status is a result, never a fault; hmmr_run_flags is not touched.
+ *   EMPTY         the track has no frame: bbox = {0, 0, 0, 0}, nothing is written to cams_crop.
+ *   NOT_FINITE    an input of the track (cams, kps, proc) or a frame's extreme is NaN / infinite, or an extreme of the track
+ *                 does not fit an int32: bbox = 0 and the track's cameras are NaN (this project's rule: the reference has
+ *                 no defined answer).
+ *   DEGENERATE    S <= 0: the cameras are what the arithmetic above gives (division by zero included).
+ *   BEYOND_START  sqrt(start . start) < sqrt(off . off) for some frame: where the reference prints 'crop is more than start
+ *                 pt..?' and stops in a debugger (:613-615).  Ordinary footage meets it; the results are those the
+ *                 reference computes when it is continued.
+ * Refused before any launch (-1, hmmr_last_error()): a null pointer, k outside [1, HMMR_TRACK_MAX_KPS], ld_kps < 2k,
+ * ld_cam < 3, n_tracks < 1, offsets that decrease, start below 0 or end beyond HMMR_TRACK_MAX_ROWS, img_h or img_w < 1,
+ * proc_size <= 0 (or NaN), a margin that is not finite.
+ * ------------------------------------------------------------------------- */
+enum { HMMR_BBOX_EMPTY = 1, HMMR_BBOX_NOT_FINITE = 2, HMMR_BBOX_DEGENERATE = 4, HMMR_BBOX_BEYOND_START = 8 };
+int hmmr_video_bbox(const float* cams, long long ld_cam, const float* kps, long long ld_kps, int k, const double* proc,
+                    double proc_size, const int32_t* offsets, int n_tracks, int img_h, int img_w, double margin,
+                    int32_t* bbox, float* cams_crop, int32_t* status, void* stream);
+
+/* ------------------------------------------------------------------------- *
  * The skeleton panel and the 2x2 collage of the demo (csrc/collage.hip; additive to ABI 19).
  *
  * hmmr_draw_skeleton replaces draw_skeleton (src/util/render/render_utils.py:38-234) as visualize_img calls it
