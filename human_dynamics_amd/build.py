@@ -43,7 +43,8 @@ def _newer(src, dst):
 
 
 def _deps():
-    return [os.path.join(CSRC, "common.h"), os.path.join(CSRC, "image_geom.h"), os.path.join(CSRC, "so3.h"), os.path.join(INCLUDE, "hmmr_hip.h")]
+    return [os.path.join(CSRC, "common.h"), os.path.join(CSRC, "image_geom.h"), os.path.join(CSRC, "so3.h"), os.path.join(CSRC, "workspace.h"),
+            os.path.join(INCLUDE, "hmmr_hip.h")]
 
 
 def build(force=False, verbose=True):

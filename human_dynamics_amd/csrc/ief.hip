@@ -12,6 +12,7 @@
 // struct's dtype.  All GEMMs go through the implicit-GEMM kernel.
 #include "common.h"
 #include "hmmr_hip.h"
+#include "workspace.h"
 
 static constexpr int LDT = 128;      // row stride of the zero-padded theta state
 // The K = 2048 / 1024 GEMMs have at most m/64 x 16 output tiles (m = kept frames of a step, a few
@@ -62,27 +63,24 @@ __global__ void ief_finalize_kernel(const float* __restrict__ theta, const float
     out[i] = v;
 }
 
-static size_t align_up(size_t v, size_t a) { return (v + a - 1) / a * a; }
-
 // One set of (pre, h1, h2, theta x 2, split-K planes) per problem of the grouped launches: the delta regressors run as ONE
 // launch per layer (hmmr_conv_desc_t.batch), each on its own set, `*_s` bytes apart; regressor 0 runs alone on set 0.
 struct IefBufs { size_t xin, pre, h1, h2, th[2], sk, skbytes, pre_s, th_s, total; };
 static IefBufs ief_layout(int m, int dtype, int group) {
     const size_t e = dtype == HMMR_BF16 ? 2 : 4;
     const size_t g = group > 1 ? group : 1;
-    IefBufs b; size_t off = 0;
-    auto take = [&](size_t bytes) { size_t o = off; off = align_up(off + bytes, 256); return o; };
-    b.xin = take((size_t)m * 2048 * e);
+    IefBufs b; WsCarver c;
+    b.xin = c.take((size_t)m * 2048 * e);
     b.pre_s = align_up((size_t)m * 1024 * e, 256);
     b.th_s = align_up((size_t)m * LDT * 4, 256);
-    b.pre = take(g * b.pre_s);
-    b.h1 = take(g * b.pre_s);
-    b.h2 = take(g * b.pre_s);
-    b.th[0] = take(g * b.th_s);
-    b.th[1] = take(g * b.th_s);
+    b.pre = c.take(g * b.pre_s);
+    b.h1 = c.take(g * b.pre_s);
+    b.h2 = c.take(g * b.pre_s);
+    b.th[0] = c.take(g * b.th_s);
+    b.th[1] = c.take(g * b.th_s);
     b.skbytes = g * hmmr_conv_splitk_workspace_bytes(m, 1024, IEF_SPLIT_K);
-    b.sk = take(b.skbytes);
-    b.total = off;
+    b.sk = c.take(b.skbytes);
+    b.total = c.total();
     return b;
 }
 
@@ -114,9 +112,9 @@ extern "C" int hmmr_ief_fwd_from(const hmmr_ief_weights_t* w, const float* strip
     HMMR_REQUIRE(m > 0, "hmmr_ief_fwd: m must be positive");
     HMMR_REQUIRE(w->num_regressors >= 1 && w->num_regressors <= HMMR_MAX_REGRESSORS, "hmmr_ief_fwd: bad num_regressors");
     HMMR_REQUIRE(w->reg[0].nd == 85, "hmmr_ief_fwd: regressor 0 must predict 85-D omega");
-    HMMR_REQUIRE(ws_bytes >= hmmr_ief_workspace_bytes(m, w->num_regressors, w->dtype), "hmmr_ief_fwd: workspace too small");
-    hipStream_t s = (hipStream_t)stream;
     const IefBufs L = ief_layout(m, w->dtype, w->num_regressors - 1);
+    HMMR_REQUIRE(ws_bytes >= L.total, "hmmr_ief_fwd: workspace too small");
+    hipStream_t s = (hipStream_t)stream;
     char* base = (char*)ws;
     const void* xin = strips;
     if (w->dtype != HMMR_F32) {

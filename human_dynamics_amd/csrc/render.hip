@@ -22,6 +22,7 @@
 #include "common.h"
 #include "hmmr_hip.h"
 #include "image_geom.h"
+#include "workspace.h"
 
 namespace {
 
@@ -42,24 +43,22 @@ struct Ws {                               // carve-up of the caller's workspace 
     float4* col;                          // [CH][nf] shaded colour
 };
 
-__host__ __device__ inline size_t align256(size_t x) { return (x + 255) & ~(size_t)255; }
-
-__host__ __device__ inline Ws carve(void* base, int ch, int nv, int nf) {
+struct WsLayout { size_t pv, fbox, bbox, rec, col, total; };      // Ws as offsets: one slab of `ch` instances (frames, or frames x tracks)
+inline WsLayout ws_layout(int ch, int nv, int nf) {
+    WsLayout l; WsCarver c;
+    l.pv = c.take((size_t)ch * nv * sizeof(float4));
+    l.fbox = c.take((size_t)ch * sizeof(int4));
+    l.bbox = c.take((size_t)ch * nf * sizeof(int2));
+    l.rec = c.take((size_t)ch * nf * sizeof(FaceRec));
+    l.col = c.take((size_t)ch * nf * sizeof(float4));
+    l.total = c.total();
+    return l;
+}
+inline Ws carve(void* base, const WsLayout& l) {
     char* p = (char*)base;
-    Ws w;
-    w.pv = (float4*)p;  p += align256((size_t)ch * nv * sizeof(float4));
-    w.fbox = (int4*)p;  p += align256((size_t)ch * sizeof(int4));
-    w.bbox = (int2*)p;  p += align256((size_t)ch * nf * sizeof(int2));
-    w.rec = (FaceRec*)p; p += align256((size_t)ch * nf * sizeof(FaceRec));
-    w.col = (float4*)p;
-    return w;
+    return Ws{(float4*)(p + l.pv), (int4*)(p + l.fbox), (int2*)(p + l.bbox), (FaceRec*)(p + l.rec), (float4*)(p + l.col)};
 }
-
-inline size_t ws_bytes(int ch, int nv, int nf) {
-    return align256((size_t)ch * nv * sizeof(float4)) + align256((size_t)ch * sizeof(int4)) +
-           align256((size_t)ch * nf * sizeof(int2)) + align256((size_t)ch * nf * sizeof(FaceRec)) +
-           align256((size_t)ch * nf * sizeof(float4));
-}
+inline int mesh_slab(int n) { return n < RENDER_CHUNK ? n : RENDER_CHUNK; }      // frames in one slab of a mesh call over n frames
 
 // subpixel index range whose centres (i + 0.5) / S - 1 may lie in [lo, hi] (ndc), widened by one subpixel so that the
 // fp32 edge tests decide at the border; clamped to [0, 2S-1] (empty: first > last)
@@ -373,6 +372,7 @@ constexpr int SCENE_SLAB = 64;            // instances per slab (bounds the work
 struct SceneTracks { hmmr_scene_track_t t[HMMR_SCENE_MAX_TRACKS]; int n; };
 
 __host__ __device__ inline int scene_slab_frames(int n_tracks) { return SCENE_SLAB / n_tracks > 1 ? SCENE_SLAB / n_tracks : 1; }
+inline int scene_slab(int n_frames, int n_tracks) { return n_frames < scene_slab_frames(n_tracks) ? n_frames : scene_slab_frames(n_tracks); }
 
 // Six waves per SIMD, as render_raster_kernel gets by itself: the face loop waits on LDS, and other waves are what hides that.
 // The bound costs two spilled registers; at the 95 registers (five waves) the compiler takes otherwise, 64 frames of one
@@ -485,7 +485,7 @@ __global__ void __launch_bounds__(THREADS, 6) scene_raster_kernel(hmmr_render_de
 
 extern "C" size_t hmmr_render_workspace_bytes(int n, int nv, int nf) {
     if (n <= 0 || n > HMMR_RENDER_MAX_FRAMES || nv <= 0 || nf <= 0 || nf > HMMR_RENDER_MAX_FACES) return 0;
-    return ws_bytes(n < RENDER_CHUNK ? n : RENDER_CHUNK, nv, nf);
+    return ws_layout(mesh_slab(n), nv, nf).total;
 }
 
 extern "C" int hmmr_render_mesh(const hmmr_render_desc_t* d, void* stream) {
@@ -508,10 +508,9 @@ extern "C" int hmmr_render_mesh(const hmmr_render_desc_t* d, void* stream) {
     HMMR_REQUIRE(d->bg_mode == HMMR_RENDER_BG_COLOR || d->bg_image, "hmmr_render_mesh: bg_mode %d without bg_image", d->bg_mode);
     HMMR_REQUIRE(d->bg_mode != HMMR_RENDER_BG_FRAME || (d->frame_h >= 1 && d->frame_w >= 1),
                  "hmmr_render_mesh: bad frame size %d x %d", d->frame_h, d->frame_w);
-    const size_t need = hmmr_render_workspace_bytes(d->n, d->nv, d->nf);
-    HMMR_REQUIRE(d->ws_bytes >= need, "hmmr_render_mesh: workspace %zu bytes < %zu", d->ws_bytes, need);
-    const int ch = d->n < RENDER_CHUNK ? d->n : RENDER_CHUNK;
-    const Ws w = carve(d->ws, ch, d->nv, d->nf);
+    const WsLayout l = ws_layout(mesh_slab(d->n), d->nv, d->nf);
+    HMMR_REQUIRE(d->ws_bytes >= l.total, "hmmr_render_mesh: workspace %zu bytes < %zu", d->ws_bytes, l.total);
+    const Ws w = carve(d->ws, l);
     const int tiles_x = (2 * d->size + TILE - 1) / TILE;
     hipStream_t st = (hipStream_t)stream;
     for (int f0 = 0; f0 < d->n; f0 += RENDER_CHUNK) {
@@ -530,8 +529,7 @@ extern "C" size_t hmmr_render_scene_workspace_bytes(int n_frames, int n_tracks, 
     if (n_frames <= 0 || n_frames > HMMR_RENDER_MAX_FRAMES || n_tracks < 1 || n_tracks > HMMR_SCENE_MAX_TRACKS || nv <= 0 ||
         nf <= 0 || nf > HMMR_RENDER_MAX_FACES)
         return 0;
-    const int cap = scene_slab_frames(n_tracks);
-    return ws_bytes((n_frames < cap ? n_frames : cap) * n_tracks, nv, nf);
+    return ws_layout(scene_slab(n_frames, n_tracks) * n_tracks, nv, nf).total;
 }
 
 extern "C" int hmmr_render_scene(const hmmr_scene_desc_t* d, void* stream) {
@@ -563,8 +561,9 @@ extern "C" int hmmr_render_scene(const hmmr_scene_desc_t* d, void* stream) {
         HMMR_REQUIRE(t.ld_verts >= 3LL * d->nv && t.ld_cam >= 3, "hmmr_render_scene: row strides of track %d smaller than the rows", k);
         tr.t[k] = t;
     }
-    const size_t need = hmmr_render_scene_workspace_bytes(d->n_frames, d->n_tracks, d->nv, d->nf);
-    HMMR_REQUIRE(d->ws_bytes >= need, "hmmr_render_scene: workspace %zu bytes < %zu", d->ws_bytes, need);
+    const int cap = scene_slab(d->n_frames, d->n_tracks);      // frames per slab, each with n_tracks instances
+    const WsLayout l = ws_layout(cap * d->n_tracks, d->nv, d->nf);
+    HMMR_REQUIRE(d->ws_bytes >= l.total, "hmmr_render_scene: workspace %zu bytes < %zu", d->ws_bytes, l.total);
 
     hmmr_render_desc_t r = {};                // what the tracks share, in hmmr_render_mesh's terms
     r.faces = d->faces;
@@ -578,8 +577,7 @@ extern "C" int hmmr_render_scene(const hmmr_scene_desc_t* d, void* stream) {
     r.frame_h = d->frame_h; r.frame_w = d->frame_w; r.out_h = d->out_h; r.out_w = d->out_w;
     r.rgb = d->rgb; r.alpha = d->alpha; r.face_index = d->face_index;
 
-    const int cap0 = scene_slab_frames(d->n_tracks), cap = d->n_frames < cap0 ? d->n_frames : cap0;
-    const Ws w = carve(d->ws, cap * d->n_tracks, d->nv, d->nf);
+    const Ws w = carve(d->ws, l);
     const int tiles_x = (2 * d->size + TILE - 1) / TILE;
     hipStream_t st = (hipStream_t)stream;
     for (int F0 = 0; F0 < d->n_frames; F0 += cap) {

@@ -22,6 +22,7 @@
 
 #include "common.h"
 #include "hmmr_hip.h"
+#include "workspace.h"
 
 // csrc/stem.hip
 int hmmr_stem_fused(const float* images, int n_real, int n, const void* wts, const float* wscale, const float* bias,
@@ -175,22 +176,21 @@ static int prof_end(Prof& p) {
     return 0;
 }
 
-static size_t align_up(size_t v, size_t a) { return (v + a - 1) / a * a; }
-
 struct ResnetBufs {
-    size_t xpad, stem, x[2], p[2], t1, t2, total;
+    size_t xpad, stem, stem_total, x[2], p[2], t1, t2, total;      // stem_total: what the unfused stem alone needs (xpad + the conv map)
 };
 static ResnetBufs resnet_layout(int n, int dtype) {
     const size_t e = dtype == HMMR_BF16 ? 2 : 4;
-    ResnetBufs b; size_t off = 0;
-    auto take = [&](size_t elems) { size_t o = off; off = align_up(off + elems * e, 256); return o; };
+    ResnetBufs b; WsCarver c;
+    auto take = [&](size_t elems) { return c.take(elems * e); };
     b.xpad = take((size_t)n * PADH * PADW * 4);
     b.stem = take((size_t)n * 112 * 112 * 64);
+    b.stem_total = c.total();
     for (int i = 0; i < 2; ++i) b.x[i] = take((size_t)n * 56 * 56 * 256);
     for (int i = 0; i < 2; ++i) b.p[i] = take((size_t)n * 56 * 56 * 256);
     b.t1 = take((size_t)n * 56 * 56 * 64);
     b.t2 = take((size_t)n * 56 * 56 * 64);
-    b.total = off;
+    b.total = c.total();
     return b;
 }
 
@@ -388,11 +388,10 @@ static int stem_run(const hmmr_resnet_weights_t* w, const hmmr_debug_t* dbg, con
 
 template <typename T>
 static int resnet_fwd_t(const hmmr_resnet_weights_t* w, const float* images, int n_real, int n, float* phi,
-                        char* ws, hipStream_t s, float* prof_ms) {
+                        char* ws, const ResnetBufs& L, hipStream_t s, float* prof_ms) {
     hmmr_unit_plan_t plan[HMMR_RESNET_UNITS];
     if (hmmr_resnet50_plan(w, n, plan)) return -1;       // (nothing has been launched yet)
     const int dt = w->dtype;
-    const ResnetBufs L = resnet_layout(n, dt);
     T* xpad = (T*)(ws + L.xpad);
     T* stem = (T*)(ws + L.stem);
     T* X[2] = {(T*)(ws + L.x[0]), (T*)(ws + L.x[1])};
@@ -499,21 +498,20 @@ extern "C" int hmmr_resnet50_fwd(const hmmr_resnet_weights_t* w, const float* im
     HMMR_REQUIRE(w && phi && ws && (images || n == 0), "hmmr_resnet50_fwd: null argument");
     HMMR_REQUIRE(n >= 0 && n_zero >= 0 && n + n_zero > 0, "hmmr_resnet50_fwd: need at least one image");
     const int nt = n + n_zero;
-    HMMR_REQUIRE(ws_bytes >= hmmr_resnet50_workspace_bytes(nt, w->dtype),
-                 "hmmr_resnet50_fwd: workspace too small (%zu < %zu)", ws_bytes,
-                 hmmr_resnet50_workspace_bytes(nt, w->dtype));
+    const ResnetBufs L = resnet_layout(nt, w->dtype);
+    HMMR_REQUIRE(ws_bytes >= L.total, "hmmr_resnet50_fwd: workspace too small (%zu < %zu)", ws_bytes, L.total);
     HMMR_REQUIRE(w->unit[0].c_in == 64 && w->unit[15].depth == 2048, "hmmr_resnet50_fwd: bad unit table");
     HMMR_REQUIRE(w->dtype == HMMR_BF16 || w->dtype == HMMR_F32 || w->dtype == HMMR_F16X3, "hmmr_resnet50_fwd: bad dtype %d", w->dtype);
     if (stem_check(w, images, hmmr_debug_state(), "hmmr_resnet50_fwd")) return -1;
-    if (w->dtype == HMMR_BF16) return resnet_fwd_t<bf16_t>(w, images, n, nt, phi, (char*)ws, (hipStream_t)stream, prof_ms);
-    if (w->dtype == HMMR_F32) return resnet_fwd_t<float>(w, images, n, nt, phi, (char*)ws, (hipStream_t)stream, prof_ms);
-    return resnet_fwd_t<bsplit_t>(w, images, n, nt, phi, (char*)ws, (hipStream_t)stream, prof_ms);
+    if (w->dtype == HMMR_BF16) return resnet_fwd_t<bf16_t>(w, images, n, nt, phi, (char*)ws, L, (hipStream_t)stream, prof_ms);
+    if (w->dtype == HMMR_F32) return resnet_fwd_t<float>(w, images, n, nt, phi, (char*)ws, L, (hipStream_t)stream, prof_ms);
+    return resnet_fwd_t<bsplit_t>(w, images, n, nt, phi, (char*)ws, L, (hipStream_t)stream, prof_ms);
 }
 
 // ---- the stem alone (include/hmmr_hip.h): what hmmr_resnet50_fwd launches first, into caller-owned tensors
 extern "C" size_t hmmr_resnet50_stem_workspace_bytes(const hmmr_resnet_weights_t* w, int n_total) {
     if (!w || n_total <= 0 || (w->dtype != HMMR_BF16 && w->dtype != HMMR_F32 && w->dtype != HMMR_F16X3)) return 0;
-    return stem_unfused(w, hmmr_debug_state()) ? resnet_layout(n_total, w->dtype).x[0] : 0;      // xpad + the conv map
+    return stem_unfused(w, hmmr_debug_state()) ? resnet_layout(n_total, w->dtype).stem_total : 0;
 }
 
 extern "C" int hmmr_resnet50_stem(const hmmr_resnet_weights_t* w, const float* images, int n, int n_zero, void* pooled, void* h1,

@@ -23,6 +23,7 @@
 #include "common.h"
 #include "hmmr_hip.h"
 #include "so3.h"
+#include "workspace.h"
 
 static constexpr int NJ = 24;
 static constexpr int NFEAT = 218;        // 1 + 10 + 207
@@ -615,13 +616,12 @@ extern "C" int hmmr_global_rigid_transformation(const float* Rs, const float* Js
 }
 
 // ------------------------------------------------------------------------- //
-static size_t align_up(size_t v, size_t a) { return (v + a - 1) / a * a; }
-
-extern "C" size_t hmmr_smpl_workspace_bytes(int m) {
-    if (m <= 0) return 0;
-    const size_t mp = ((size_t)m + IBM - 1) / IBM * IBM;       // the verts kernels read whole instance groups
-    return align_up(mp * LDF * 4, 256) + align_up(mp * LDA * 4, 256);
+struct SmplBufs { size_t feat, A, total; };
+static SmplBufs smpl_layout(int m) {
+    WsCarver c; const size_t mp = ((size_t)m + IBM - 1) / IBM * IBM;       // the verts kernels read whole instance groups
+    return {c.take(mp * LDF * 4), c.take(mp * LDA * 4), c.total()};      // (a braced list is evaluated left to right)
 }
+extern "C" size_t hmmr_smpl_workspace_bytes(int m) { return m > 0 ? smpl_layout(m).total : 0; }
 
 static int smpl_launch(const hmmr_smpl_consts_t* c, const float* theta, int ld_theta, const float* beta,
                        int ld_beta, const float* cams, int ld_cam, int m, float* verts, float* joints,
@@ -631,13 +631,13 @@ static int smpl_launch(const hmmr_smpl_consts_t* c, const float* theta, int ld_t
     HMMR_REQUIRE(c && theta && beta && verts && joints && ws, "hmmr_smpl_fwd: null argument");
     HMMR_REQUIRE(m > 0, "hmmr_smpl_fwd: m must be positive");
     HMMR_REQUIRE(c->lbs_nnz >= 1 && c->lbs_nnz <= NJ, "hmmr_smpl_fwd: lbs_nnz=%d out of range", c->lbs_nnz);
-    HMMR_REQUIRE(ws_bytes >= hmmr_smpl_workspace_bytes(m), "hmmr_smpl_fwd: workspace too small");
+    const SmplBufs L = smpl_layout(m);
+    HMMR_REQUIRE(ws_bytes >= L.total, "hmmr_smpl_fwd: workspace too small");
     HMMR_REQUIRE(!kps || cams, "hmmr_smpl_fwd: kps requested without cams");
     HMMR_REQUIRE(c->vpad >= (c->num_verts + VT - 1) / VT * VT && c->vpad % VT == 0,
                  "hmmr_smpl_fwd: dirs row stride vpad=%d must be a multiple of %d covering num_verts=%d", c->vpad, VT, c->num_verts);
     hipStream_t s = (hipStream_t)stream;
-    float* feat = (float*)ws;
-    float* A = (float*)((char*)ws + align_up(((size_t)m + IBM - 1) / IBM * IBM * LDF * 4, 256));
+    float *feat = (float*)((char*)ws + L.feat), *A = (float*)((char*)ws + L.A);
     const int vtiles = (c->num_verts + VT - 1) / VT;
     hipLaunchKernelGGL(smpl_pose_kernel, dim3((m + 7) / 8), dim3(256), 0, s, theta, ld_theta, beta, ld_beta,
                        c->j_template, c->j_shapedirs, c->parents, m, feat, A, rs, ld_rs, rm);

@@ -8,6 +8,7 @@
 // only the GEMM operands take the struct's dtype.
 #include "common.h"
 #include "hmmr_hip.h"
+#include "workspace.h"
 
 #define GN_EPS 1e-6f
 // K = 3*2048 is long and M = b*t is short (640 rows for 32 windows): 4 K-slices quadruple the
@@ -87,14 +88,21 @@ extern "C" int hmmr_groupnorm_relu(const float* x, const float* gamma, const flo
     return 0;
 }
 
-static size_t align_up(size_t v, size_t a) { return (v + a - 1) / a * a; }
+// One layout for both f_movie stages: `nop` row buffers [m][2048] of the operand dtype, then `nf32` fp32 ones, then the split-K partial planes
+struct MovieBufs { size_t buf[4], sk, skbytes, total; };
+static MovieBufs movie_layout(size_t m, int dtype, int nop, int nf32) {
+    MovieBufs l = {}; WsCarver c;
+    for (int i = 0; i < nop + nf32; ++i) l.buf[i] = c.take(m * 2048 * (i < nop && dtype == HMMR_BF16 ? 2 : 4));
+    l.skbytes = hmmr_conv_splitk_workspace_bytes((int)m, 2048, TEMPORAL_SPLIT_K_MAX);
+    l.sk = c.take(l.skbytes);
+    l.total = c.total();
+    return l;
+}
+static MovieBufs temporal_layout(int b, int t, int dtype) { return movie_layout((size_t)b * t, dtype, 1, 3); }      // h | h1, net[0], net[1]
+static MovieBufs hallucinator_layout(int m, int dtype) { return movie_layout((size_t)m, dtype, 3, 0); }             // x, h1, h2
 
 extern "C" size_t hmmr_temporal_workspace_bytes(int b, int t, int dtype) {
-    if (b <= 0 || t <= 0) return 0;
-    const size_t m = (size_t)b * t, e = dtype == HMMR_BF16 ? 2 : 4;
-    // h (operand dtype) + h1 (fp32) + two fp32 trunk buffers + split-K partial planes
-    return align_up(m * 2048 * e, 256) + 3 * align_up(m * 2048 * 4, 256) +
-           align_up(hmmr_conv_splitk_workspace_bytes((int)m, 2048, TEMPORAL_SPLIT_K_MAX), 256);
+    return b > 0 && t > 0 ? temporal_layout(b, t, dtype).total : 0;
 }
 
 extern "C" int hmmr_temporal_fwd(const hmmr_temporal_weights_t* w, const float* phi, int b, int t,
@@ -102,17 +110,12 @@ extern "C" int hmmr_temporal_fwd(const hmmr_temporal_weights_t* w, const float* 
     HMMR_REQUIRE(w && phi && strips && ws, "hmmr_temporal_fwd: null argument");
     HMMR_REQUIRE(b > 0 && t > 0, "hmmr_temporal_fwd: bad shape");
     HMMR_REQUIRE(w->num_blocks >= 1 && w->num_blocks <= HMMR_MAX_TEMPORAL_BLOCKS, "hmmr_temporal_fwd: bad num_blocks");
-    HMMR_REQUIRE(ws_bytes >= hmmr_temporal_workspace_bytes(b, t, w->dtype), "hmmr_temporal_fwd: workspace too small");
+    const MovieBufs L = temporal_layout(b, t, w->dtype);
+    HMMR_REQUIRE(ws_bytes >= L.total, "hmmr_temporal_fwd: workspace too small");
     const int C = 2048;
-    const size_t m = (size_t)b * t, e = w->dtype == HMMR_BF16 ? 2 : 4;
-    char* p = (char*)ws;
-    void* h = p;              p += align_up(m * C * e, 256);
-    float* h1 = (float*)p;    p += align_up(m * C * 4, 256);
-    float* net[2];
-    net[0] = (float*)p;       p += align_up(m * C * 4, 256);
-    net[1] = (float*)p;       p += align_up(m * C * 4, 256);
-    void* skws = p;
-    const size_t skbytes = hmmr_conv_splitk_workspace_bytes((int)m, C, TEMPORAL_SPLIT_K_MAX);
+    char* base = (char*)ws;
+    void* h = base + L.buf[0];
+    float *h1 = (float*)(base + L.buf[1]), *net[2] = {(float*)(base + L.buf[2]), (float*)(base + L.buf[3])};
     const float* cur = phi;
     for (int i = 0; i < w->num_blocks; ++i) {
         const hmmr_temporal_block_t& B = w->block[i];
@@ -124,7 +127,7 @@ extern "C" int hmmr_temporal_fwd(const hmmr_temporal_weights_t* w, const float* 
         d.n_img = b; d.hin = t; d.win = 1; d.cin = C;
         d.in_img_stride = (int64_t)t * C; d.in_row_stride = C; d.in_px_stride = C;
         d.kh = 3; d.kw = 1; d.sy = d.sx = 1; d.py = 1; d.px = 0; d.ho = t; d.wo = 1; d.cout = C; d.ldo = C;
-        d.split_k = temporal_split_k(w->dtype); d.ws = skws; d.ws_bytes = skbytes;
+        d.split_k = temporal_split_k(w->dtype); d.ws = base + L.sk; d.ws_bytes = L.skbytes;
         if (hmmr_conv_gemm(&d, stream)) return -2;
         if (hmmr_groupnorm_relu(h1, B.gn2_gamma, B.gn2_beta, b, t, C, 32, h, w->dtype, stream)) return -2;
         d.w = B.conv2.w; d.scale = B.conv2.scale; d.shift = B.conv2.shift; d.tile = B.conv2.tile;
@@ -139,10 +142,7 @@ extern "C" int hmmr_temporal_fwd(const hmmr_temporal_weights_t* w, const float* 
 // Hallucinator fc2_res (src/models.py:270-296, pred_mode == 'hal'):
 //   phi + fc3(relu(fc2(relu(fc1(phi)))))     three 2048x2048 fully-connected layers.
 extern "C" size_t hmmr_hallucinator_workspace_bytes(int m, int dtype) {
-    if (m <= 0) return 0;
-    const size_t e = dtype == HMMR_BF16 ? 2 : 4;
-    return 3 * align_up((size_t)m * 2048 * e, 256) +
-           align_up(hmmr_conv_splitk_workspace_bytes(m, 2048, TEMPORAL_SPLIT_K_MAX), 256);
+    return m > 0 ? hallucinator_layout(m, dtype).total : 0;
 }
 
 template <typename TO>
@@ -158,15 +158,11 @@ extern "C" int hmmr_hallucinator_fwd(const hmmr_hallucinator_weights_t* w, const
                                      float* out, void* ws, size_t ws_bytes, void* stream) {
     HMMR_REQUIRE(w && phi && out && ws, "hmmr_hallucinator_fwd: null argument");
     HMMR_REQUIRE(m > 0, "hmmr_hallucinator_fwd: m must be positive");
-    HMMR_REQUIRE(ws_bytes >= hmmr_hallucinator_workspace_bytes(m, w->dtype), "hmmr_hallucinator_fwd: workspace too small");
+    const MovieBufs L = hallucinator_layout(m, w->dtype);
+    HMMR_REQUIRE(ws_bytes >= L.total, "hmmr_hallucinator_fwd: workspace too small");
     const int C = 2048;
-    const size_t e = w->dtype == HMMR_BF16 ? 2 : 4;
-    char* p = (char*)ws;
-    void* x = p;  p += align_up((size_t)m * C * e, 256);
-    void* h1 = p; p += align_up((size_t)m * C * e, 256);
-    void* h2 = p; p += align_up((size_t)m * C * e, 256);
-    void* sk = p;
-    const size_t skb = hmmr_conv_splitk_workspace_bytes(m, C, TEMPORAL_SPLIT_K_MAX);
+    char* base = (char*)ws;
+    void *x = base + L.buf[0], *h1 = base + L.buf[1], *h2 = base + L.buf[2];
     hipStream_t s = (hipStream_t)stream;
     const void* xin = phi;
     if (w->dtype != HMMR_F32) {
@@ -186,7 +182,7 @@ extern "C" int hmmr_hallucinator_fwd(const hmmr_hallucinator_weights_t* w, const
         d.in_img_stride = C; d.in_row_stride = C; d.in_px_stride = C;
         d.kh = d.kw = 1; d.sy = d.sx = 1; d.ho = d.wo = 1; d.cout = C; d.ldo = C;
         d.relu = relu; d.res = res; d.ldr = C;
-        d.split_k = 4; d.ws = sk; d.ws_bytes = skb;            // (the hallucinator keeps 4 slices in every mode)
+        d.split_k = 4; d.ws = base + L.sk; d.ws_bytes = L.skbytes;            // (the hallucinator keeps 4 slices in every mode)
         return hmmr_conv_gemm(&d, s);
     };
     if (fc(xin, w->fc1, h1, w->dtype, 1, nullptr)) return -2;

@@ -19,6 +19,7 @@
 
 #include "common.h"
 #include "hmmr_hip.h"
+#include "workspace.h"
 
 namespace {
 constexpr int TRACK_TILE = HMMR_TRACK_TILE;       // rows per scan step = threads of every workgroup here
@@ -250,13 +251,20 @@ __global__ void track_geom_kernel(Chunk c, int track0, const int* __restrict__ r
         for (int a = 0; a < 5; ++a) info[row * 5 + a] = o[a];
 }
 
+// three double planes [3][n] and two int planes [n] for n = max(rows, 1), packed: 80 bytes per row, no 256-byte rounding
+struct TrackOffs { size_t box, interp, med, valid, next, total; };
+TrackOffs track_layout(int n_total) {
+    const size_t n = n_total > 0 ? n_total : 1;
+    WsCarver c;
+    return {c.take(24 * n, 8), c.take(24 * n, 8), c.take(24 * n, 8), c.take(4 * n, 4), c.take(4 * n, 4), c.total()};   // (braces: left to right)
+}
+// the workspace check and carve of hmmr_track_bbox and hmmr_track_smooth
 struct Layout { double *box, *interp, *med; int *valid, *next; };
-size_t layout_bytes(long long n) { return (size_t)n * (9 * sizeof(double) + 2 * sizeof(int)); }
-Layout carve(void* ws, long long n) {
-    Layout l;
-    l.box = (double*)ws; l.interp = l.box + 3 * n; l.med = l.interp + 3 * n;
-    l.valid = (int*)(l.med + 3 * n); l.next = l.valid + n;
-    return l;
+int carve(const char* who, char* ws, size_t ws_bytes, int n_total, Layout* out) {
+    const TrackOffs l = track_layout(n_total);
+    HMMR_REQUIRE(ws_bytes >= l.total, "%s: workspace of %zu bytes, need %zu", who, ws_bytes, l.total);
+    *out = Layout{(double*)(ws + l.box), (double*)(ws + l.interp), (double*)(ws + l.med), (int*)(ws + l.valid), (int*)(ws + l.next)};
+    return 0;
 }
 
 // offsets: n_tracks + 1 non-decreasing row numbers, the first >= 0, the last within what 32-bit element indices can address
@@ -310,7 +318,7 @@ int smooth(const int32_t* offsets, int n_tracks, const int* range, const double*
 
 extern "C" size_t hmmr_track_workspace_bytes(int n_total, int n_tracks) {
     if (n_total < 0 || n_total > HMMR_TRACK_MAX_ROWS || n_tracks < 1) return 0;
-    return layout_bytes(n_total > 0 ? n_total : 1);
+    return track_layout(n_total).total;
 }
 
 extern "C" int hmmr_track_bbox(const double* kps, const unsigned char* present, const int32_t* offsets, int n_tracks, int k,
@@ -324,9 +332,8 @@ extern "C" int hmmr_track_bbox(const double* kps, const unsigned char* present, 
     Weights g;
     if (check_filters(who, kernel_size, gauss_w, gauss_radius, g)) return -1;
     const int row0 = offsets[0], n = offsets[n_tracks] - offsets[0];
-    HMMR_REQUIRE(ws_bytes >= hmmr_track_workspace_bytes(offsets[n_tracks], n_tracks), "%s: workspace of %zu bytes, need %zu", who, ws_bytes,
-                 hmmr_track_workspace_bytes(offsets[n_tracks], n_tracks));
-    const Layout l = carve(ws, offsets[n_tracks] > 0 ? offsets[n_tracks] : 1);
+    Layout l;
+    if (carve(who, (char*)ws, ws_bytes, offsets[n_tracks], &l)) return -1;
     if (n > 0) {
         hipLaunchKernelGGL(track_box_kernel, dim3((unsigned)((n + TRACK_TILE - 1) / TRACK_TILE)), dim3(TRACK_TILE), 0, stream, kps, present,
                            row0, n, k, vis_thresh, l.box, l.valid);
@@ -349,9 +356,8 @@ extern "C" int hmmr_track_smooth(const double* params, const int32_t* offsets, i
     if (check_offsets(who, offsets, n_tracks)) return -1;
     Weights g;
     if (check_filters(who, kernel_size, gauss_w, gauss_radius, g)) return -1;
-    HMMR_REQUIRE(ws_bytes >= hmmr_track_workspace_bytes(offsets[n_tracks], n_tracks), "%s: workspace of %zu bytes, need %zu", who, ws_bytes,
-                 hmmr_track_workspace_bytes(offsets[n_tracks], n_tracks));
-    const Layout l = carve(ws, offsets[n_tracks] > 0 ? offsets[n_tracks] : 1);
+    Layout l;
+    if (carve(who, (char*)ws, ws_bytes, offsets[n_tracks], &l)) return -1;
     return smooth(offsets, n_tracks, nullptr, params, l.med, kernel_size, g, out, (hipStream_t)stream);
 }
 

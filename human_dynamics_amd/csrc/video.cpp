@@ -10,6 +10,7 @@
 #include <initializer_list>
 
 #include "hmmr_hip.h"
+#include "workspace.h"
 
 void hmmr_set_error(const char* fmt, ...);
 int hmmr_tracks_plan_as(const char* who, const int32_t* track_offsets, int n_tracks, int T, int fov, int max_frames, int max_windows,
@@ -20,7 +21,6 @@ int hmmr_tracks_plan_as(const char* who, const int32_t* track_offsets, int n_tra
 namespace {
 
 constexpr int C = 2048;                  // feature width (phi, movie strips)
-inline size_t align_up(size_t v) { return (v + 255) & ~(size_t)255; }
 inline int imin(int a, int b) { return a < b ? a : b; }
 
 // the carve of `ws`: phi, then ONE region that first serves the ResNet passes and afterwards the tail passes (same stream: in order)
@@ -77,22 +77,21 @@ void tail_needs_add(const hmmr_model_t* m, int T, const TailPass& t, TailNeeds* 
 int carve(const hmmr_model_t* m, const char* who, int n, int resnet_frames, int T, const TailNeeds& need, Carve* out) {
     Carve c = {};
     const int R = m->ief->num_regressors;
-    size_t off = 0;
-    c.phi = off; off += align_up((size_t)(n + 1) * C * 4);
-    c.region = off;
+    WsCarver outer, tail;                                // tail: offsets inside the region
+    c.phi = outer.take((size_t)(n + 1) * C * 4);
     c.resnet_bytes = hmmr_resnet50_workspace_bytes(resnet_frames + 1, m->resnet->dtype);
     VIDEO_REQUIRE(c.resnet_bytes > 0, "%s: no ResNet workspace for this dtype", who);
-    size_t t = 0;
-    c.windows = t; t += align_up((size_t)need.mw * T * C * 4);
-    c.strips = t;  t += align_up((size_t)need.mw * T * C * 4);
-    c.kept = t;    t += align_up((size_t)need.mk * C * 4);
-    c.omegas = t;  t += align_up((size_t)R * need.mk * 85 * 4);
+    c.windows = tail.take((size_t)need.mw * T * C * 4);
+    c.strips = tail.take((size_t)need.mw * T * C * 4);
+    c.kept = tail.take((size_t)need.mk * C * 4);
+    c.omegas = tail.take((size_t)R * need.mk * 85 * 4);
     c.movie_bytes = need.movie_bytes; c.ief_bytes = need.ief_bytes; c.smpl_bytes = need.smpl_bytes;
     VIDEO_REQUIRE(c.movie_bytes && c.ief_bytes && c.smpl_bytes, "%s: a stage reports no workspace for this model", who);
-    c.movie_ws = t; t += align_up(c.movie_bytes);
-    c.ief_ws = t;   t += align_up(c.ief_bytes);
-    c.smpl_ws = t;  t += align_up(c.smpl_bytes);
-    c.total = c.region + (t > align_up(c.resnet_bytes) ? t : align_up(c.resnet_bytes));
+    c.movie_ws = tail.take(c.movie_bytes);
+    c.ief_ws = tail.take(c.ief_bytes);
+    c.smpl_ws = tail.take(c.smpl_bytes);
+    c.region = outer.take(tail.total() > c.resnet_bytes ? tail.total() : c.resnet_bytes);      // the union: ResNet passes first, tail passes after
+    c.total = outer.total();
     *out = c;
     return 0;
 }
