@@ -43,8 +43,8 @@ def _newer(src, dst):
 
 
 def _deps():
-    return [os.path.join(CSRC, "common.h"), os.path.join(CSRC, "image_geom.h"), os.path.join(CSRC, "so3.h"), os.path.join(CSRC, "workspace.h"),
-            os.path.join(INCLUDE, "hmmr_hip.h")]
+    # every header of csrc/: a new one cannot be forgotten
+    return sorted(os.path.join(CSRC, h) for h in os.listdir(CSRC) if h.endswith(".h")) + [os.path.join(INCLUDE, "hmmr_hip.h")]
 
 
 def build(force=False, verbose=True):

@@ -34,19 +34,11 @@
 //     waits on the ring / patch / shortcut are COUNTED s_waitcnt vmcnt(N), N from a compile-time table of the schedule.
 // Rounding points, product order (w.hi x.lo, w.lo x.hi, w.hi x.hi) and K order are those of the launches it replaces
 // (conv3x3_stream tiles 19 / 20, then gemm_conv.hip's conv3 and conv1): bit-identical, tested per kernel and through the ResNet.
-#include <type_traits>
-#include <utility>
-
-#include "common.h"
-#include "hmmr_hip.h"
+#include "stream_kit.h"
 
 namespace {
 
-typedef const __attribute__((address_space(1))) void* gptr_t;
-typedef __attribute__((address_space(3))) void* lptr_t;
 typedef __attribute__((ext_vector_type(2))) unsigned u32x2;
-
-__device__ u32x4 g_b1_dump[64];             // 1 KB: where the stores of rows beyond M go
 
 struct B1Args {
     const char* h1;                         // [M][64] split rows (256 B): conv2's input
@@ -133,18 +125,6 @@ constexpr int b1_wait_n(int s, int kc3, bool res) {
     return b1_cum(s - 1, 2, kc3, res) - cover;
 }
 
-// s_waitcnt vmcnt(N) lgkmcnt(0) (gfx9 encoding: vmcnt[3:0] | expcnt[6:4] | lgkmcnt[11:8] | vmcnt_hi[15:14])
-template <int N> __device__ __forceinline__ void b1_wait() {
-    static_assert(N >= 0 && N < 64, "vmcnt is a 6-bit counter");
-    __builtin_amdgcn_s_waitcnt((N & 15) | (7 << 4) | (0 << 8) | ((N >> 4) << 14));
-}
-
-template <int V> using b1_ic = std::integral_constant<int, V>;
-// f(b1_ic<0>{}), f(b1_ic<1>{}), ... in order
-template <class F, int... I> __device__ __forceinline__ void b1_for(F&& f, std::integer_sequence<int, I...>) { (f(b1_ic<I>{}), ...); }
-
-struct xfrag { shalf8 hi, lo; };            // MFMA B-operand fragment: 32 pixels x 16 channels
-
 // D layout of a 32-channel block (nh / nl[g][i]: the packed hi / lo halves of channels 8 g + 4 lh + 2 i, + 1 of pixel lr) -> the two
 // B-operand fragments of its 16-wide K chunks (lane (lr, lh): channels 16 k + 8 lh .. + 7): one v_permlane32_swap per register pair
 __device__ __forceinline__ void b1_d_to_b(const shalf2 (&nh)[4][2], const shalf2 (&nl)[4][2], xfrag (&th)[2]) {
@@ -167,12 +147,7 @@ __device__ __forceinline__ void b1_d_to_b(const shalf2 (&nh)[4][2], const shalf2
 // ---- the epilogues' arithmetic.  Two waves per SIMD share one vector issue port, and the unit does ~18 values per lane and 32 output
 // channels: the instruction COUNT is what the kernel's skeleton costs (the first version, written with split4 and float conversions,
 // spent 22 vector instructions per value: 0.32 ms of a 0.6 ms launch with the MFMAs and the HBM traffic taken out, profiles/r05b).
-// split2_mix / split4_mix (common.h): the split in that form.
-__device__ __forceinline__ void b1_split2(float c0, float c1, unsigned& h, unsigned& l) { split2_mix(c0, c1, h, l); }
-// the value a packed (hi, lo) pair holds: hi + lo, exact before its one rounding to fp32 (= (float)hi + (float)lo); low / high half of the dwords
-__device__ __forceinline__ float b1_sum_lo(unsigned h, unsigned l) { return split_sum_lo(h, l); }
-__device__ __forceinline__ float b1_sum_hi(unsigned h, unsigned l) { return split_sum_hi(h, l); }
-__device__ __forceinline__ void b1_split4(const float (&v)[4], float lo_clamp, unsigned (&h)[2], unsigned (&l)[2], float& satm) { split4_mix(v, lo_clamp, h, l, satm); }
+// split2_mix / split4_mix / split_sum_lo / split_sum_hi (common.h): the split and hi + lo in that form.
 
 // mma3 (common.h), or under probe bit 1 something that only keeps its operands alive
 __device__ __forceinline__ f32x16 b1_mma3(const wfrag& w, const shalf8& xh, const shalf8& xl, f32x16 c) {
@@ -236,8 +211,8 @@ __global__ __launch_bounds__(256, 2) void b1_unit_kernel(const B1Args a) {
         const int r = 8 * q + rsub, m = mbase + r;
         const int ls = pslot ^ ((r >> 1) & 7);
         const bool ok = m < a.M && !B1_PROBE(2);
-        orow[q] = ok ? a.out + (long long)m * DEPTH + ls * 4 : (bsplit_t*)g_b1_dump + lane * 4;
-        hrow[q] = ok ? a.out_h1 + (long long)m * 64 + ls * 4 : (bsplit_t*)g_b1_dump + lane * 4;
+        orow[q] = ok ? a.out + (long long)m * DEPTH + ls * 4 : (bsplit_t*)g_dump_page + lane * 4;
+        hrow[q] = ok ? a.out_h1 + (long long)m * 64 + ls * 4 : (bsplit_t*)g_dump_page + lane * 4;
         ostep[q] = ok ? 32 : 0;
         rrow[q] = RES ? a.res + (long long)(ok ? m : 0) * a.ldr + ls * 4 : nullptr;
     }
@@ -316,9 +291,9 @@ __global__ __launch_bounds__(256, 2) void b1_unit_kernel(const B1Args a) {
     auto slab_step = [&](auto s_c) {
         constexpr int S = decltype(s_c)::value;
         __builtin_amdgcn_sched_barrier(0);
-        if constexpr (B1_PROBE(4)) b1_wait<63>();
-        else if constexpr (S >= NS - 1) b1_wait<b1_wait_n(S, KC3, RES)>();
-        else b1_wait<63>();                                     // (lgkmcnt(0) alone: slabs 0 .. 3 landed in the prologue)
+        if constexpr (B1_PROBE(4)) wait_vm_lgkm0<63>();
+        else if constexpr (S >= NS - 1) wait_vm_lgkm0<b1_wait_n(S, KC3, RES)>();
+        else wait_vm_lgkm0<63>();                                     // (lgkmcnt(0) alone: slabs 0 .. 3 landed in the prologue)
         if (!B1_PROBE(4)) __builtin_amdgcn_s_barrier();
         asm volatile("" ::: "memory");
         __builtin_amdgcn_sched_barrier(0);
@@ -377,19 +352,19 @@ __global__ __launch_bounds__(256, 2) void b1_unit_kernel(const B1Args a) {
     };
     Slab2 fa, fb;
     Slab1 fA;                                                   // conv3 fragments of the chunk about to start
-    slab_step(b1_ic<0>{});
-    read_slab2(b1_ic<0>{}, fa);
+    slab_step(ic<0>{});
+    read_slab2(ic<0>{}, fa);
     auto slab_pair = [&](auto s_c) {                            // slabs S (in fa) and S + 1 (in fb), S even
         constexpr int S = decltype(s_c)::value;
-        slab_step(b1_ic<S + 1>{});
-        read_slab2(b1_ic<S + 1>{}, fb);
+        slab_step(ic<S + 1>{});
+        read_slab2(ic<S + 1>{}, fb);
         mma_slab2(fa);
-        slab_step(b1_ic<S + 2>{});                              // (S + 2 = 18: the first slab of the tail, conv3 chunk 0)
-        if constexpr (S + 2 < B1_CONV2_SLABS) read_slab2(b1_ic<S + 2>{}, fa);
+        slab_step(ic<S + 2>{});                              // (S + 2 = 18: the first slab of the tail, conv3 chunk 0)
+        if constexpr (S + 2 < B1_CONV2_SLABS) read_slab2(ic<S + 2>{}, fa);
         else read_slab1(S + 2, fA);
         mma_slab2(fb);
     };
-    b1_for([&](auto i_c) { slab_pair(b1_ic<2 * decltype(i_c)::value>{}); }, std::make_integer_sequence<int, B1_CONV2_SLABS / 2>{});
+    static_for([&](auto i_c) { slab_pair(ic<2 * decltype(i_c)::value>{}); }, std::make_integer_sequence<int, B1_CONV2_SLABS / 2>{});
 
     B1_STAMP(2);
     // ---- conv2's epilogue: folded BN + ReLU, split, D layout -> the h2 panel as B-operand fragments
@@ -405,7 +380,7 @@ __global__ __launch_bounds__(256, 2) void b1_unit_kernel(const B1Args a) {
 #pragma unroll
             for (int e = 0; e < 4; ++e) v[e] = fmaf(acc[j][4 * g + e], s4[e], b4[e]);
             unsigned h[2], l[2];
-            b1_split4(v, 0.f, h, l, satm);                      // (ReLU and the clamp to the fp16 range are one v_med3_f32)
+            split4_mix(v, 0.f, h, l, satm);                      // (ReLU and the clamp to the fp16 range are one v_med3_f32)
 #pragma unroll
             for (int i = 0; i < 2; ++i) { nh[g][i] = __builtin_bit_cast(shalf2, h[i]); nl[g][i] = __builtin_bit_cast(shalf2, l[i]); }
         }
@@ -430,7 +405,7 @@ __global__ __launch_bounds__(256, 2) void b1_unit_kernel(const B1Args a) {
 #pragma unroll
         for (int kc = 0; kc < 4; ++kc) dst = b1_mma3(fA.w[kc], xh[kc].hi, xh[kc].lo, dst);
         if constexpr (KC3B > 0) {
-            slab_step(b1_ic<SA + 1>{});
+            slab_step(ic<SA + 1>{});
             Slab1 fA2;
             read_slab1(SA + 1, fA2);
 #pragma unroll
@@ -438,18 +413,18 @@ __global__ __launch_bounds__(256, 2) void b1_unit_kernel(const B1Args a) {
         }
     };
     f32x16 accP, accQ;                                         // conv3 accumulators of even / odd chunks
-    conv3(b1_ic<0>{}, accP);
+    conv3(ic<0>{}, accP);
     auto chunk = [&](auto c_c) {
         constexpr int C = decltype(c_c)::value, SB = b1_step_b(C, KC3), B = C & 1;
         f32x16& acc1 = (C & 1) ? accQ : accP;
         // software pipeline: the MFMAs of conv3 chunk C + 1 are issued in front of the epilogue of chunk C, which then runs beside them
         if constexpr (C + 1 < NCH) {
-            slab_step(b1_ic<b1_step_a(C + 1, KC3)>{});
+            slab_step(ic<b1_step_a(C + 1, KC3)>{});
             read_slab1(b1_step_a(C + 1, KC3), fA);
-            conv3(b1_ic<C + 1>{}, (C & 1) ? accP : accQ);
+            conv3(ic<C + 1>{}, (C & 1) ? accP : accQ);
         }
         // the conv1' fragments of this chunk are requested in front of the epilogue
-        slab_step(b1_ic<SB>{});
+        slab_step(ic<SB>{});
         Slab1 fB;
         read_slab1(SB, fB);
         // * scale3 + shift3 (+ shortcut), split, IN PLACE into the staging tile; the pre-activation of the STORED value
@@ -459,22 +434,22 @@ __global__ __launch_bounds__(256, 2) void b1_unit_kernel(const B1Args a) {
         for (int g = 0; g < 4; ++g) {
             const int ch = C * 32 + 8 * g + 4 * lh;
             const f32x4 s4 = *(const f32x4*)(sS3 + ch), b4 = *(const f32x4*)(sB3 + ch);
-            char* ph = stg + lr * 128 + (((2 * g) ^ sw) << 4) + 8 * lh;
-            char* pl = stg + lr * 128 + (((2 * g + 1) ^ sw) << 4) + 8 * lh;
+            char* ph = stage_slot(stg, lr, lh, g, sw, 0);
+            char* pl = stage_slot(stg, lr, lh, g, sw, 1);
             float v[4];
 #pragma unroll
             for (int e = 0; e < 4; ++e) v[e] = fmaf(acc1[4 * g + e], s4[e], b4[e]);
             if constexpr (RES) {
                 const unsigned long long h = *(const unsigned long long*)ph, l = *(const unsigned long long*)pl;
-                v[0] += b1_sum_lo((unsigned)h, (unsigned)l);
-                v[1] += b1_sum_hi((unsigned)h, (unsigned)l);
-                v[2] += b1_sum_lo((unsigned)(h >> 32), (unsigned)(l >> 32));
-                v[3] += b1_sum_hi((unsigned)(h >> 32), (unsigned)(l >> 32));
+                v[0] += split_sum_lo((unsigned)h, (unsigned)l);
+                v[1] += split_sum_hi((unsigned)h, (unsigned)l);
+                v[2] += split_sum_lo((unsigned)(h >> 32), (unsigned)(l >> 32));
+                v[3] += split_sum_hi((unsigned)(h >> 32), (unsigned)(l >> 32));
             }
             unsigned oh[2], ol[2];
             if constexpr (B1_PROBE(8)) {
                 oh[0] = __float_as_uint(v[0]); oh[1] = __float_as_uint(v[1]); ol[0] = __float_as_uint(v[2]); ol[1] = __float_as_uint(v[3]);
-            } else b1_split4(v, -HMMR_SPLIT_MAX, oh, ol, satm);
+            } else split4_mix(v, -HMMR_SPLIT_MAX, oh, ol, satm);
             *(unsigned long long*)ph = (unsigned long long)oh[0] | ((unsigned long long)oh[1] << 32);
             *(unsigned long long*)pl = (unsigned long long)ol[0] | ((unsigned long long)ol[1] << 32);
             if constexpr (B1_PROBE(8)) {
@@ -485,14 +460,14 @@ __global__ __launch_bounds__(256, 2) void b1_unit_kernel(const B1Args a) {
             // the next unit's pre-activation of the value AS STORED (hi + lo), ReLU'd, clamped and split again
             const f32x4 ps = *(const f32x4*)(sPS + ch), pb = *(const f32x4*)(sPB + ch);
             float y[4];
-            y[0] = fmaf(b1_sum_lo(oh[0], ol[0]), ps[0], pb[0]);
-            y[1] = fmaf(b1_sum_hi(oh[0], ol[0]), ps[1], pb[1]);
-            y[2] = fmaf(b1_sum_lo(oh[1], ol[1]), ps[2], pb[2]);
-            y[3] = fmaf(b1_sum_hi(oh[1], ol[1]), ps[3], pb[3]);
+            y[0] = fmaf(split_sum_lo(oh[0], ol[0]), ps[0], pb[0]);
+            y[1] = fmaf(split_sum_hi(oh[0], ol[0]), ps[1], pb[1]);
+            y[2] = fmaf(split_sum_lo(oh[1], ol[1]), ps[2], pb[2]);
+            y[3] = fmaf(split_sum_hi(oh[1], ol[1]), ps[3], pb[3]);
             unsigned qh[2], ql[2];
 #pragma unroll
             for (int i = 0; i < 2; ++i) {
-                b1_split2(split_relu(y[2 * i]), split_relu(y[2 * i + 1]), qh[i], ql[i]);
+                split2_mix(split_relu(y[2 * i]), split_relu(y[2 * i + 1]), qh[i], ql[i]);
                 nh[g][i] = __builtin_bit_cast(shalf2, qh[i]); nl[g][i] = __builtin_bit_cast(shalf2, ql[i]);
             }
         }
@@ -520,7 +495,7 @@ __global__ __launch_bounds__(256, 2) void b1_unit_kernel(const B1Args a) {
             for (int j = 0; j < 2; ++j) acc2[j] = b1_mma3(fB.w[kcl * 2 + j], th[kcl].hi, th[kcl].lo, acc2[j]);
         B1_STAMP(4 + C);
     };
-    b1_for(chunk, std::make_integer_sequence<int, NCH>{});
+    static_for(chunk, std::make_integer_sequence<int, NCH>{});
 
     // ---- conv1' epilogue: BN (+ ReLU), split, through this wave's staging tiles, coalesced stores
     __builtin_amdgcn_sched_barrier(0);
@@ -536,9 +511,8 @@ __global__ __launch_bounds__(256, 2) void b1_unit_kernel(const B1Args a) {
 #pragma unroll
             for (int e = 0; e < 4; ++e) v[e] = fmaf(acc2[j][4 * g + e], s4[e], b4[e]);
             unsigned oh[2], ol[2];
-            b1_split4(v, lo1, oh, ol, satm);
-            *(unsigned long long*)(stg + lr * 128 + (((2 * g) ^ sw) << 4) + 8 * lh) = (unsigned long long)oh[0] | ((unsigned long long)oh[1] << 32);
-            *(unsigned long long*)(stg + lr * 128 + (((2 * g + 1) ^ sw) << 4) + 8 * lh) = (unsigned long long)ol[0] | ((unsigned long long)ol[1] << 32);
+            split4_mix(v, lo1, oh, ol, satm);
+            stage_store_group(stg, lr, lh, g, sw, oh, ol);
         }
         u32x4 xr[4];
 #pragma unroll
@@ -556,13 +530,7 @@ int launch_b1(const B1Args& base, hipStream_t stream) {
     a.n_tiles = (a.M + B1_BM - 1) / B1_BM;
     auto kern = b1_unit_kernel<KC3B, RES>;
     static DeviceOnce once;
-    if (const unsigned long long bit = once.due()) {
-        HMMR_CHECK_HIP(hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, B1_LDS));
-        once.mark(bit);
-    }
-    hipLaunchKernelGGL(kern, dim3((unsigned)a.n_tiles), dim3(256), B1_LDS, stream, a);
-    HMMR_CHECK_HIP(hipGetLastError());
-    return 0;
+    return launch_with_lds(kern, once, dim3((unsigned)a.n_tiles), dim3(256), B1_LDS, B1_LDS, stream, a);
 }
 
 }  // namespace
@@ -594,6 +562,6 @@ int hmmr_b1_unit_split(const hmmr_tail_desc_t* d, hipStream_t stream) {
     a.scale1 = d->scale1; a.shift1 = d->shift1; a.relu1 = d->relu1; a.out_h1 = (bsplit_t*)d->out_h1;
     a.M = d->m; a.H = d->hin; a.W = d->win;
     if (B1_PROBE(64))       // (development build: the stamp buffer's address travels in the reserved debug words, like the other probe builds')
-        a.ts = (unsigned long long*)(((unsigned long long)(unsigned)hmmr_debug_state()->reserved[1] << 32) | (unsigned)hmmr_debug_state()->reserved[0]);
+        a.ts = probe_stamp_buffer();
     return folded ? launch_b1<4, false>(a, stream) : launch_b1<0, true>(a, stream);
 }

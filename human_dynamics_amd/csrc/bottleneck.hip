@@ -41,8 +41,7 @@
 //          pre-activated and the launch ends.
 // So a whole bottleneck unit of blocks 1-2 is one launch:
 //   [conv shortcut] + conv2 + conv3 + add + [next preact + next conv1].
-#include "common.h"
-#include "hmmr_hip.h"
+#include "stream_kit.h"
 
 namespace {
 
@@ -420,13 +419,7 @@ int launch_tail(const TailArgs& a, hipStream_t stream) {
     static_assert(!CONV2 || 2 * (BM * 128 + CM * 128) <= Cfg::OFF_C, "conv2 stages must fit below the constants");
     auto kern = bottleneck_tail_kernel<BM, CM, NCH, N2, CONV2, SC, PH2>;
     static DeviceOnce once;              // per kernel instantiation, per device
-    if (const unsigned long long bit = once.due()) {
-        HMMR_CHECK_HIP(hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, Cfg::LDS));
-        once.mark(bit);
-    }
-    hipLaunchKernelGGL(kern, dim3((unsigned)((a.M + BM - 1) / BM)), dim3(NT), Cfg::LDS, stream, a);
-    HMMR_CHECK_HIP(hipGetLastError());
-    return 0;
+    return launch_with_lds(kern, once, dim3((unsigned)((a.M + BM - 1) / BM)), dim3(NT), Cfg::LDS, Cfg::LDS, stream, a);
 }
 
 }  // namespace

@@ -18,8 +18,7 @@
 //   * workgroups are 4 waves on 64 pixels (168-VGPR budget at three waves per SIMD).
 // Global tensors keep the interleaved split layout ([hi8][lo8] per 8 channels): a 64-channel chunk of a row is 256
 // contiguous bytes = 16 slots, staged by 16 lanes (even slots -> hi plane, odd -> lo plane).
-#include "common.h"
-#include "hmmr_hip.h"
+#include "stream_kit.h"
 
 namespace {
 
@@ -39,9 +38,6 @@ struct SplitTailArgs {
     const char* w2f;                            // conv2 filters packed [64+][9 * 64] like every hmmr_layer_t.w, K = (ky, kx, ci)
     const float* scale2; const float* shift2;
 };
-
-__device__ __forceinline__ float bf_lo(unsigned v) { return shalf_lo(v); }
-__device__ __forceinline__ float bf_hi(unsigned v) { return shalf_hi(v); }
 
 // KS: 64-channel K sub-tiles of conv3 (1: h2 of block 1; 2: h2 of block 2, or block 1's {h2, xp} with the shortcut folded)
 // NCH = depth / 64, N2 = conv1' output channels, RES: a shortcut tensor is added (false: it is folded into conv3's K)
@@ -278,10 +274,10 @@ __global__ __launch_bounds__(256, NCH > 4 ? 2 : 3) void tail_split_kernel(const 
             for (int j = 0; j < 4; ++j) v[j] = fmaf(acc1[4 * g + j], s4[j], b4[j]);    // (scale3 absent -> 1.0f: == acc + b)
             if constexpr (RES) {
                 const unsigned long long h = *(const unsigned long long*)ph, l = *(const unsigned long long*)(ph + PLANE);
-                v[0] += bf_lo((unsigned)h) + bf_lo((unsigned)l);
-                v[1] += bf_hi((unsigned)h) + bf_hi((unsigned)l);
-                v[2] += bf_lo((unsigned)(h >> 32)) + bf_lo((unsigned)(l >> 32));
-                v[3] += bf_hi((unsigned)(h >> 32)) + bf_hi((unsigned)(l >> 32));
+                v[0] += shalf_lo((unsigned)h) + shalf_lo((unsigned)l);
+                v[1] += shalf_hi((unsigned)h) + shalf_hi((unsigned)l);
+                v[2] += shalf_lo((unsigned)(h >> 32)) + shalf_lo((unsigned)(l >> 32));
+                v[3] += shalf_hi((unsigned)(h >> 32)) + shalf_hi((unsigned)(l >> 32));
             }
             unsigned long long oh, ol;
             split4(v, oh, ol, satmask);
@@ -355,13 +351,7 @@ int launch_split_tail(const SplitTailArgs& a, hipStream_t stream) {
     constexpr int lds = (CONV2 ? 1 : KS) * 2 * 64 * 128 + xreg + 4 * NCH * 64 * (int)sizeof(float);
     auto kern = tail_split_kernel<KS, NCH, N2, RES, CONV2>;
     static DeviceOnce once;
-    if (const unsigned long long bit = once.due()) {
-        HMMR_CHECK_HIP(hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, lds));
-        once.mark(bit);
-    }
-    hipLaunchKernelGGL(kern, dim3((unsigned)((a.M + 63) / 64)), dim3(256), lds, stream, a);     // (CONV2: M = images x H x W, 64 | H W)
-    HMMR_CHECK_HIP(hipGetLastError());
-    return 0;
+    return launch_with_lds(kern, once, dim3((unsigned)((a.M + 63) / 64)), dim3(256), lds, lds, stream, a);     // (CONV2: M = images x H x W, 64 | H W)
 }
 
 }  // namespace

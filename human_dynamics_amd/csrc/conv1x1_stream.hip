@@ -25,18 +25,9 @@
 // other's loop -- for short K loops and the conv3 form's HBM-heavy epilogue.  DESIGN.md section 4.1.3 has the measurements.
 // Products and their order per output element: (w.hi x.lo, w.lo x.hi, w.hi x.hi) per 16-channel K step, steps in channel order -- the
 // same for every tile of this kernel (they differ from gemm_conv.hip's 32-channel steps by fp32 rounding of the accumulation only).
-#include <type_traits>
-#include <utility>
-
-#include "common.h"
-#include "hmmr_hip.h"
+#include "stream_kit.h"
 
 namespace {
-
-typedef const __attribute__((address_space(1))) void* gptr_t;
-typedef __attribute__((address_space(3))) void* lptr_t;
-
-__device__ u32x4 g_s1_dump[64 + 32];       // where the stores of rows beyond M go (a lane's 16 bytes, up to 4 row blocks of 128 B further)
 
 struct S1Args {
     const char* in;                         // [M][C] split rows
@@ -63,27 +54,11 @@ struct S1Args {
 #endif
 #define S1_PROBE(bit) (((S1_PROBE_BITS) & (bit)) != 0)
 
-// s_waitcnt vmcnt(N) lgkmcnt(0) (gfx9 encoding: vmcnt[3:0] | expcnt[6:4] | lgkmcnt[11:8] | vmcnt_hi[15:14])
-template <int N> __device__ __forceinline__ void s1_wait() {
-    static_assert(N >= 0 && N < 64, "vmcnt is a 6-bit counter");
-    __builtin_amdgcn_s_waitcnt((N & 15) | (7 << 4) | (0 << 8) | ((N >> 4) << 14));
-}
-
-// the loop's LDS reads as inline assembly: the compiler does not track them; a step ends with one lgkmcnt(0) of its own
-template <int OFF> __device__ __forceinline__ shalf8 s1_rd(unsigned addr) {
-    shalf8 v; asm volatile("ds_read_b128 %0, %1 offset:%2" : "=v"(v) : "v"(addr), "n"(OFF)); return v;
-}
-
-struct xfrag { shalf8 hi, lo; };            // MFMA B-operand fragment: 32 pixels x 16 channels
-
-template <int V> using s1_ic = std::integral_constant<int, V>;
-
+// (the loop's LDS reads are lds_rd128: untracked, a step ends with one lgkmcnt(0) of its own)
 // a group of D steps; steps past the last one (cin / 16 need not be a multiple of D) are skipped by a scalar branch
 template <typename F, int... S> __device__ __forceinline__ void s1_group(F&& f, int kt0, int nk, std::integer_sequence<int, S...>) {
-    ((kt0 + S < nk ? f(s1_ic<S>{}, kt0 + S) : (void)0), ...);
+    ((kt0 + S < nk ? f(ic<S>{}, kt0 + S) : (void)0), ...);
 }
-
-template <typename F, int... Bs> __device__ __forceinline__ void s1_blocks(F&& f, std::integer_sequence<int, Bs...>) { (f(s1_ic<Bs>{}), ...); }
 
 // FM x FN accumulators per wave, WGM x WGN waves: the tile is 32 WGM FM pixels x 128 channels; D: ring depth of both operands
 // EPI 0: scale / shift / relu, column split.  EPI 1: conv3 of a bottleneck unit -- IN2: the folded shortcut's operand, RES: the shortcut tensor,
@@ -117,7 +92,7 @@ __global__ __launch_bounds__(256, OCC) void conv1x1_stream_kernel(const S1Args a
     const int m0 = mt * BM;
     const int nk = a.nk;
     const int wm = wave / WGN, wn = wave - wm * WGN;
-    const unsigned lds0 = (unsigned)(unsigned long long)(lptr_t)smem;
+    const unsigned lds0 = lds_addr(smem);
 
     // ---- this tile's folded BN constants (128 scales, 128 shifts): loaded before any DMA request is in flight, stored behind the rings
     const float cv = tid < 128 ? a.scale[nt * 128 + tid] : a.shift[nt * 128 + tid - 128];
@@ -191,7 +166,7 @@ __global__ __launch_bounds__(256, OCC) void conv1x1_stream_kernel(const S1Args a
     auto read_one = [&](int set, int r, int slot_) {            // all constants after unrolling
         if (r < 2 * FN) {
             const int j = r >> 1, pl = r & 1;
-#define S1_F(SL, J, PL) if (slot_ == SL && j == J && pl == PL) { shalf8 v = s1_rd<SL * SLAB + J * 2048 + PL * 1024>(vW); if (PL) fw[set][J].lo = v; else fw[set][J].hi = v; }
+#define S1_F(SL, J, PL) if (slot_ == SL && j == J && pl == PL) { shalf8 v = lds_rd128<shalf8, SL * SLAB + J * 2048 + PL * 1024>(vW); if (PL) fw[set][J].lo = v; else fw[set][J].hi = v; }
 #define S1_FJ(SL, J) S1_F(SL, J, 0) S1_F(SL, J, 1)
 #define S1_FS(SL) if constexpr (SL < D) { S1_FJ(SL, 0) if constexpr (FN > 1) { S1_FJ(SL, 1) } if constexpr (FN > 2) { S1_FJ(SL, 2) S1_FJ(SL, 3) } }
             S1_FS(0) S1_FS(1) S1_FS(2) S1_FS(3) S1_FS(4) S1_FS(5)
@@ -200,7 +175,7 @@ __global__ __launch_bounds__(256, OCC) void conv1x1_stream_kernel(const S1Args a
 #undef S1_F
         } else {
             const int i = (r - 2 * FN) >> 1, pl = (r - 2 * FN) & 1;
-#define S1_X(I) if constexpr (I < FM) { if (i == I) { if (pl) fx[set][I].lo = s1_rd<I * 2048>(adcurl); else fx[set][I].hi = s1_rd<I * 2048>(adcur); } }
+#define S1_X(I) if constexpr (I < FM) { if (i == I) { if (pl) fx[set][I].lo = lds_rd128<shalf8, I * 2048>(adcurl); else fx[set][I].hi = lds_rd128<shalf8, I * 2048>(adcur); } }
             S1_X(0) S1_X(1) S1_X(2) S1_X(3) S1_X(4) S1_X(5) S1_X(6) S1_X(7) S1_X(8) S1_X(9) S1_X(10) S1_X(11) S1_X(12) S1_X(13) S1_X(14) S1_X(15)
 #undef S1_X
         }
@@ -212,14 +187,14 @@ __global__ __launch_bounds__(256, OCC) void conv1x1_stream_kernel(const S1Args a
 
     // ---- prologue: stage 0, the fragments of step 0, then stage 1
     __builtin_amdgcn_sched_barrier(0);
-    s1_wait<(D - 1) * P>();
+    wait_vm_lgkm0<(D - 1) * P>();
     __builtin_amdgcn_s_barrier();
     __builtin_amdgcn_sched_barrier(0);
     slot_setup(0);
 #pragma unroll
     for (int r = 0; r < NR; ++r) read_one(0, r, 0);
     __builtin_amdgcn_sched_barrier(0);
-    s1_wait<(D - 2) * P>();
+    wait_vm_lgkm0<(D - 2) * P>();
     __builtin_amdgcn_s_barrier();
     __builtin_amdgcn_sched_barrier(0);
 
@@ -252,9 +227,9 @@ __global__ __launch_bounds__(256, OCC) void conv1x1_stream_kernel(const S1Args a
                     __builtin_amdgcn_sched_barrier(0);
                 }
         // stage kt + 2 (read during step kt + 1) has landed; stages kt + 3 .. kt + D stay in flight
-        if (S1_PROBE(4)) __builtin_amdgcn_s_waitcnt(63 | (7 << 4) | (0 << 8) | (3 << 14));      // lgkmcnt(0) alone
-        else if (S1_PROBE(8)) s1_wait<(D - 2) * RW>();
-        else s1_wait<(D - 2) * P>();
+        if (S1_PROBE(4)) wait_lgkm<0>();
+        else if (S1_PROBE(8)) wait_vm_lgkm0<(D - 2) * RW>();
+        else wait_vm_lgkm0<(D - 2) * P>();
         __builtin_amdgcn_sched_barrier(0);
         if (!S1_PROBE(16)) __builtin_amdgcn_s_barrier();
         __builtin_amdgcn_sched_barrier(0);
@@ -262,7 +237,7 @@ __global__ __launch_bounds__(256, OCC) void conv1x1_stream_kernel(const S1Args a
     for (int kt0 = 0; kt0 < nk; kt0 += U) s1_group(step, kt0, nk, std::make_integer_sequence<int, U>{});
     // (the requests of the last steps -- repeats of the last stage -- land in the rings the epilogue is about to reuse)
     __builtin_amdgcn_sched_barrier(0);
-    s1_wait<0>();
+    wait_vm_lgkm0<0>();
     __builtin_amdgcn_s_barrier();
     __builtin_amdgcn_sched_barrier(0);
 
@@ -323,7 +298,7 @@ __global__ __launch_bounds__(256, OCC) void conv1x1_stream_kernel(const S1Args a
                 }
         }
         asm volatile("" ::: "memory");
-        if constexpr (RES) s1_blocks([&](auto b_c) { res_dma(decltype(b_c)::value); }, std::make_integer_sequence<int, (PD < B ? PD : B)>{});
+        if constexpr (RES) static_for([&](auto b_c) { res_dma(decltype(b_c)::value); }, std::make_integer_sequence<int, (PD < B ? PD : B)>{});
         float satmax = 0.f;
         auto block = [&](auto b_c) {
             constexpr int b = decltype(b_c)::value, i = b / FN, j = b % FN;
@@ -332,7 +307,7 @@ __global__ __launch_bounds__(256, OCC) void conv1x1_stream_kernel(const S1Args a
                 if constexpr (b + PD < B) res_dma(b + PD);
                 // younger than shortcut block b: the shortcut blocks b + 1 .. b + PD and the stores of blocks b - PD .. b - 1
                 constexpr int ahead = (B - 1 - b) < PD ? (B - 1 - b) : PD, behind = b < PD ? b : PD;
-                s1_wait<4 * ahead + NST * behind>();
+                wait_vm_lgkm0<4 * ahead + NST * behind>();
                 asm volatile("" ::: "memory");
             }
             char* to = wv + (b % NSTG) * 4096;
@@ -340,7 +315,7 @@ __global__ __launch_bounds__(256, OCC) void conv1x1_stream_kernel(const S1Args a
             const char* rt = wv + 2 * NSTG * 4096 + (b % RT) * 4096;
 #pragma unroll
             for (int g = 0; g < 4; ++g) {
-                const unsigned oh_ = lr * 128 + (((2 * g) ^ sw) << 4) + 8 * lh, ol_ = lr * 128 + (((2 * g + 1) ^ sw) << 4) + 8 * lh;
+                const unsigned oh_ = stage_slot(0, lr, lh, g, sw, 0), ol_ = stage_slot(0, lr, lh, g, sw, 1);
                 float c[4];
                 f32x4 sv, bv, s2v = {}, b2v = {};
                 if constexpr (CREG) {
@@ -397,11 +372,11 @@ __global__ __launch_bounds__(256, OCC) void conv1x1_stream_kernel(const S1Args a
             for (int q = 0; q < 4; ++q) {
                 bool valid;
                 const unsigned off = row_off(i, q, valid);
-                *(u32x4*)(valid ? out_t + off + j * 128 : (char*)g_s1_dump + lane * 16) = xr[q];
-                if constexpr (OUT2) *(u32x4*)(valid ? out2_t + off + j * 128 : (char*)g_s1_dump + lane * 16) = x2[q];
+                *(u32x4*)(valid ? out_t + off + j * 128 : (char*)g_dump_page + lane * 16) = xr[q];
+                if constexpr (OUT2) *(u32x4*)(valid ? out2_t + off + j * 128 : (char*)g_dump_page + lane * 16) = x2[q];
             }
         };
-        s1_blocks(block, std::make_integer_sequence<int, B>{});
+        static_for(block, std::make_integer_sequence<int, B>{});
         split_flag_max(satmax);
         return;
     }
@@ -437,7 +412,7 @@ __global__ __launch_bounds__(256, OCC) void conv1x1_stream_kernel(const S1Args a
         for (int q = 0; q < 4; ++q) {
             const int r = 8 * q + rsub, m = mb + r;
             const int ls = pslot ^ ((r >> 1) & 7);
-            orow[q] = m < a.M ? obase + (long long)m * ldo + nb + ls * 4 : (bsplit_t*)g_s1_dump + lane * 4;
+            orow[q] = m < a.M ? obase + (long long)m * ldo + nb + ls * 4 : (bsplit_t*)g_dump_page + lane * 4;
         }
 #pragma unroll
         for (int j = 0; j < FN; ++j, ++blk) {
@@ -456,8 +431,7 @@ __global__ __launch_bounds__(256, OCC) void conv1x1_stream_kernel(const S1Args a
                 split2_mix(c[2], c[3], h23, l23);
                 const unsigned long long oh = (unsigned long long)h01 | ((unsigned long long)h23 << 32);
                 const unsigned long long ol = (unsigned long long)l01 | ((unsigned long long)l23 << 32);
-                *(unsigned long long*)(tile + lr * 128 + (((2 * g) ^ sw) << 4) + 8 * lh) = oh;
-                *(unsigned long long*)(tile + lr * 128 + (((2 * g + 1) ^ sw) << 4) + 8 * lh) = ol;
+                stage_store_group(tile, lr, lh, g, sw, oh, ol);
             }
             u32x4 xr[4];
 #pragma unroll
@@ -478,13 +452,7 @@ int launch_s1(const S1Args& base, hipStream_t stream) {
     a.n_tiles = ((a.M + BM - 1) / BM) * a.tiles_n;
     auto kern = conv1x1_stream_kernel<FM, FN, WGM, WGN, D, EPI, IN2, RES, OUT2, OCC>;
     static DeviceOnce once;
-    if (const unsigned long long bit = once.due()) {
-        HMMR_CHECK_HIP(hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, lds));
-        once.mark(bit);
-    }
-    hipLaunchKernelGGL(kern, dim3((unsigned)a.n_tiles), dim3(256), lds, stream, a);
-    HMMR_CHECK_HIP(hipGetLastError());
-    return 0;
+    return launch_with_lds(kern, once, dim3((unsigned)a.n_tiles), dim3(256), lds, lds, stream, a);
 }
 
 // the conv3 form of a tile shape: which of in2 / res / out2 the launch has picks the instantiation

@@ -29,17 +29,9 @@
 // Products and their order per output element: (w.hi x.lo, w.lo x.hi, w.hi x.hi) per K step, K steps in stream order -- the
 // same for every tile shape, so every tile of this kernel produces the same bits (they differ from k_order 0 / 1 by the fp32
 // rounding of a different summation order only).
-#include <type_traits>
-
-#include "common.h"
-#include "hmmr_hip.h"
+#include "stream_kit.h"
 
 namespace {
-
-typedef const __attribute__((address_space(1))) void* gptr_t;
-typedef __attribute__((address_space(3))) void* lptr_t;
-
-__device__ u32x4 g_s3_dump[64 + 32];       // where the stores of rows beyond M go (a lane's 16 bytes, up to 4 row blocks of 128 B further)
 
 struct S3Args {
     const char* in;                         // [M][C] split rows
@@ -65,23 +57,8 @@ struct S3Args {
 #define S3_STAMP(k) do { } while (0)
 #endif
 
-// s_waitcnt vmcnt(N) lgkmcnt(0) (gfx9 encoding: vmcnt[3:0] | expcnt[6:4] | lgkmcnt[11:8] | vmcnt_hi[15:14])
-template <int N> __device__ __forceinline__ void s3_wait() {
-    static_assert(N >= 0 && N < 64, "vmcnt is a 6-bit counter");
-    __builtin_amdgcn_s_waitcnt((N & 15) | (7 << 4) | (0 << 8) | ((N >> 4) << 14));
-}
-
-// the loop's LDS reads as inline assembly: the compiler does not track them (it would wait lgkmcnt(0) at the first use of any of
-// them); the step ends with one lgkmcnt(0) of its own
-template <int OFF> __device__ __forceinline__ shalf8 s3_rd(unsigned addr) {
-    shalf8 v; asm volatile("ds_read_b128 %0, %1 offset:%2" : "=v"(v) : "v"(addr), "n"(OFF)); return v;
-}
-
-struct xfrag { shalf8 hi, lo; };            // MFMA B-operand fragment: 32 pixels x 16 channels
-
+// (the loop's LDS reads are lds_rd128: untracked, the step ends with one lgkmcnt(0) of its own)
 constexpr int S3_NS = 6;                    // ring slabs; a slab = one K step of a tile's NB row blocks (32 channels each) x (hi 1 KB | lo 1 KB)
-
-template <int V> using s3_ic = std::integral_constant<int, V>;
 
 // FM x FN accumulators per wave, WGM x WGN waves: the tile is 32 WGM FM pixels x 32 WGN FN channels (128 or 64); WMAX: the widest image
 // SPLIT: f16x3 operands (a K step = 16 channels as hi and lo halves: three MFMAs per product); false: bf16 operands (the same 64-byte
@@ -115,7 +92,7 @@ __global__ __launch_bounds__(256, 1) void conv3x3_stream_kernel(const S3Args a) 
     const int base = m0 - W - 1;                                // input pixel of patch row 0
     const int nc = a.nc, nk = 9 * nc;
     const int wm = wave / WGN, wn = wave - wm * WGN;
-    const unsigned lds0 = (unsigned)(unsigned long long)(lptr_t)smem;
+    const unsigned lds0 = lds_addr(smem);
 
     // ---- patch DMA: piece q of this wave = rows 64 q + 16 wave .. + 15, four lanes per row (one coalesced 64-byte chunk; as quarter
     // planes with one lane per row the same bytes cost four times the L1 transactions and 5 % of the kernel, profiles/r04d).  Rows
@@ -192,7 +169,7 @@ __global__ __launch_bounds__(256, 1) void conv3x3_stream_kernel(const S3Args a) 
         constexpr int TAP_ = decltype(tap_c)::value, KY = TAP_ / 3, KX = TAP_ % 3;
         if (r < 2 * FN) {
             const int j = r >> 1, pl = r & 1;
-#define S3_F(SL, J, PL) if (slot_ == SL && j == J && pl == PL) { shalf8 v = s3_rd<SL * SLAB + J * 2048 + PL * 1024>(vW); if (PL) fw[set][J].lo = v; else fw[set][J].hi = v; }
+#define S3_F(SL, J, PL) if (slot_ == SL && j == J && pl == PL) { shalf8 v = lds_rd128<shalf8, SL * SLAB + J * 2048 + PL * 1024>(vW); if (PL) fw[set][J].lo = v; else fw[set][J].hi = v; }
 #define S3_FJ(SL, J) S3_F(SL, J, 0) S3_F(SL, J, 1)
 #define S3_FS(SL) S3_FJ(SL, 0) if constexpr (FN > 1) { S3_FJ(SL, 1) } if constexpr (FN > 2) { S3_FJ(SL, 2) S3_FJ(SL, 3) }
             S3_FS(0) S3_FS(1) S3_FS(2) S3_FS(3) S3_FS(4) S3_FS(5)
@@ -212,7 +189,7 @@ __global__ __launch_bounds__(256, 1) void conv3x3_stream_kernel(const S3Args a) 
                                  : "=&v"(adcur), "=v"(adcurl) : "s"(my | mx), "v"(A0), "v"(Zb), "v"(A0l), "v"(Zbl) : "vcc");
                 }
             }
-#define S3_X(I) if constexpr (I < FM) { if (i == I) { if (pl) fx[set][I].lo = s3_rd<I * 2048>(adcurl); else fx[set][I].hi = s3_rd<I * 2048>(adcur); } }
+#define S3_X(I) if constexpr (I < FM) { if (i == I) { if (pl) fx[set][I].lo = lds_rd128<shalf8, I * 2048>(adcurl); else fx[set][I].hi = lds_rd128<shalf8, I * 2048>(adcur); } }
             S3_X(0) S3_X(1) S3_X(2) S3_X(3) S3_X(4) S3_X(5) S3_X(6) S3_X(7) S3_X(8) S3_X(9) S3_X(10) S3_X(11) S3_X(12) S3_X(13) S3_X(14) S3_X(15)
 #undef S3_X
         }
@@ -230,14 +207,14 @@ __global__ __launch_bounds__(256, 1) void conv3x3_stream_kernel(const S3Args a) 
 
     // ---- prologue: patch 0 and stage 0, then the fragments of step 0
     __builtin_amdgcn_sched_barrier(0);
-    s3_wait<RW * (NS - 1)>();
+    wait_vm_lgkm0<RW * (NS - 1)>();
     __builtin_amdgcn_s_barrier();
     __builtin_amdgcn_sched_barrier(0);
-    tap_setup(s3_ic<0>{}, 0);
+    tap_setup(ic<0>{}, 0);
 #pragma unroll
-    for (int r = 0; r < NR; ++r) read_one(s3_ic<0>{}, 0, r, 0);
+    for (int r = 0; r < NR; ++r) read_one(ic<0>{}, 0, r, 0);
     __builtin_amdgcn_sched_barrier(0);
-    s3_wait<RW * (NS - 2)>();                                   // ... stage 1 too, and the fragments of step 0
+    wait_vm_lgkm0<RW * (NS - 2)>();                                   // ... stage 1 too, and the fragments of step 0
     __builtin_amdgcn_s_barrier();
     __builtin_amdgcn_sched_barrier(0);
     S3_STAMP(1);
@@ -269,26 +246,26 @@ __global__ __launch_bounds__(256, 1) void conv3x3_stream_kernel(const S3Args a) 
                     }
                     const int g = (NP * i + p) * FN + j;
                     if (g == 0 && more && !S3_PROBE(4)) ring_dma(kt + NS, SUB);
-                    if (g == 1 && !S3_PROBE(16)) tap_setup(s3_ic<TAP1>{}, BUF1);           // (past the last step: a harmless read of stale LDS)
+                    if (g == 1 && !S3_PROBE(16)) tap_setup(ic<TAP1>{}, BUF1);           // (past the last step: a harmless read of stale LDS)
                     if (TAP == 0 && g >= 2 && g < 2 + NPP && pat && !S3_PROBE(4) && !S3_PROBE(64)) patch_piece(g - 2 < NPP ? g - 2 : 0, c + 1, BUFP);
 #pragma unroll
                     for (int r = 0; r < NR; ++r)
-                        if (2 + (r * (NG - 4)) / NR == g && !S3_PROBE(2)) read_one(s3_ic<TAP1>{}, NXT, r, SNEXT);
+                        if (2 + (r * (NG - 4)) / NR == g && !S3_PROBE(2)) read_one(ic<TAP1>{}, NXT, r, SNEXT);
                     __builtin_amdgcn_sched_barrier(0);
                 }
         // stage kt + 2 (read during step kt + 1) has landed; younger requests stay in flight: stages kt + 3 .. kt + 6 and, through
         // taps 0 .. 4, the patch of the next chunk (issued behind the ring stage of tap 0; vmcnt retires in order)
-        if (S3_PROBE(4) || S3_PROBE(32)) __builtin_amdgcn_s_waitcnt(63 | (7 << 4) | (0 << 8) | (3 << 14));      // lgkmcnt(0) alone
-        else if (more) { if (TAP <= 4 && c + 1 < nc && !S3_PROBE(64)) s3_wait<RW * (NS - 2) + NPP>(); else s3_wait<RW * (NS - 2)>(); }
-        else s3_wait<0>();
+        if (S3_PROBE(4) || S3_PROBE(32)) wait_lgkm<0>();
+        else if (more) { if (TAP <= 4 && c + 1 < nc && !S3_PROBE(64)) wait_vm_lgkm0<RW * (NS - 2) + NPP>(); else wait_vm_lgkm0<RW * (NS - 2)>(); }
+        else wait_vm_lgkm0<0>();
         __builtin_amdgcn_sched_barrier(0);
         if (!S3_PROBE(8)) __builtin_amdgcn_s_barrier();
         __builtin_amdgcn_sched_barrier(0);
     };
     auto chunk_pair = [&](int kt0, int c0, auto... S) { (step(S, kt0 + decltype(S)::value, c0 + decltype(S)::value / 9), ...); };
     for (int c0 = 0; c0 < nc; c0 += 2)
-        chunk_pair(18 * (c0 >> 1), c0, s3_ic<0>{}, s3_ic<1>{}, s3_ic<2>{}, s3_ic<3>{}, s3_ic<4>{}, s3_ic<5>{}, s3_ic<6>{}, s3_ic<7>{}, s3_ic<8>{},
-                   s3_ic<9>{}, s3_ic<10>{}, s3_ic<11>{}, s3_ic<12>{}, s3_ic<13>{}, s3_ic<14>{}, s3_ic<15>{}, s3_ic<16>{}, s3_ic<17>{});
+        chunk_pair(18 * (c0 >> 1), c0, ic<0>{}, ic<1>{}, ic<2>{}, ic<3>{}, ic<4>{}, ic<5>{}, ic<6>{}, ic<7>{}, ic<8>{},
+                   ic<9>{}, ic<10>{}, ic<11>{}, ic<12>{}, ic<13>{}, ic<14>{}, ic<15>{}, ic<16>{}, ic<17>{});
     S3_STAMP(2);
 
     // ---- epilogue: D layout (lane = pixel, 4 consecutive channels per register group) -> folded BN, ReLU, split -> this wave's
@@ -322,7 +299,7 @@ __global__ __launch_bounds__(256, 1) void conv3x3_stream_kernel(const S3Args a) 
             for (int q = 0; q < 4; ++q) {
                 const int r = 8 * q + rsub, m = mb + r;
                 const int ls = pslot ^ ((r >> 1) & 7);
-                orow[q] = m < a.M ? (bsplit_t*)a.out + (long long)m * a.ldo + nb + ls * 4 : (bsplit_t*)g_s3_dump + lane * 4;
+                orow[q] = m < a.M ? (bsplit_t*)a.out + (long long)m * a.ldo + nb + ls * 4 : (bsplit_t*)g_dump_page + lane * 4;
             }
     #pragma unroll
             for (int j = 0; j < FN; ++j, ++blk) {
@@ -339,6 +316,8 @@ __global__ __launch_bounds__(256, 1) void conv3x3_stream_kernel(const S3Args a) 
                     const unsigned h01 = __builtin_bit_cast(unsigned, shalf2{(shalf_t)c[0], (shalf_t)c[1]});
                     const unsigned h23 = __builtin_bit_cast(unsigned, shalf2{(shalf_t)c[2], (shalf_t)c[3]});
                     // lo = fp16(c - hi): c - hi is exact in fp32, so the mixed-precision fma rounds once, like the cast of split4 (common.h)
+                    // (split2_mix's two instructions, written out: both hi pairs are converted in front of the four v_fma_mix, and two
+                    //  calls of split2_mix compile to a different instruction stream in 12 of this kernel's forms, profiles/stream_kit.log)
                     unsigned l01, l23;
                     asm("v_fma_mixlo_f16 %0, %1, -1.0, %2 op_sel_hi:[1,0,0]" : "=v"(l01) : "v"(h01), "v"(c[0]));
                     asm("v_fma_mixhi_f16 %0, %1, -1.0, %2 op_sel:[1,0,0] op_sel_hi:[1,0,0]" : "+v"(l01) : "v"(h01), "v"(c[1]));
@@ -346,8 +325,7 @@ __global__ __launch_bounds__(256, 1) void conv3x3_stream_kernel(const S3Args a) 
                     asm("v_fma_mixhi_f16 %0, %1, -1.0, %2 op_sel:[1,0,0] op_sel_hi:[1,0,0]" : "+v"(l23) : "v"(h23), "v"(c[3]));
                     const unsigned long long oh = (unsigned long long)h01 | ((unsigned long long)h23 << 32);
                     const unsigned long long ol = (unsigned long long)l01 | ((unsigned long long)l23 << 32);
-                    *(unsigned long long*)(tile + lr * 128 + (((2 * g) ^ sw) << 4) + 8 * lh) = oh;
-                    *(unsigned long long*)(tile + lr * 128 + (((2 * g + 1) ^ sw) << 4) + 8 * lh) = ol;
+                    stage_store_group(tile, lr, lh, g, sw, oh, ol);
                 }
                 u32x4 xr[4];
     #pragma unroll
@@ -369,7 +347,7 @@ __global__ __launch_bounds__(256, 1) void conv3x3_stream_kernel(const S3Args a) 
             for (int q = 0; q < 2; ++q) {
                 const int r = 16 * q + (lane >> 2), m = mb + r;
                 const int ls = (lane & 3) ^ ((r >> 2) & 3);
-                orow[q] = m < a.M ? (bf16_t*)a.out + (long long)m * a.ldo + nb + ls * 8 : (bf16_t*)g_s3_dump + lane * 8;
+                orow[q] = m < a.M ? (bf16_t*)a.out + (long long)m * a.ldo + nb + ls * 8 : (bf16_t*)g_dump_page + lane * 8;
             }
 #pragma unroll
             for (int j = 0; j < FN; ++j, ++blk) {
@@ -408,13 +386,7 @@ int launch_s3_t(const S3Args& base, int cout, hipStream_t stream) {
     a.nt_stride = (long long)9 * a.nc * (NB * 2048);
     auto kern = conv3x3_stream_kernel<FM, FN, WGM, WGN, WMAX, SPLIT>;
     static DeviceOnce once;
-    if (const unsigned long long bit = once.due()) {
-        HMMR_CHECK_HIP(hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, lds));
-        once.mark(bit);
-    }
-    hipLaunchKernelGGL(kern, dim3((unsigned)a.n_tiles), dim3(256), lds, stream, a);
-    HMMR_CHECK_HIP(hipGetLastError());
-    return 0;
+    return launch_with_lds(kern, once, dim3((unsigned)a.n_tiles), dim3(256), lds, lds, stream, a);
 }
 
 template <int FM, int FN, int WGM, int WGN, int WMAX>
@@ -444,7 +416,7 @@ int hmmr_conv3x3_stream(const hmmr_conv_desc_t* d, hipStream_t stream) {
     a.M = d->n_img * d->ho * d->wo; a.H = d->hin; a.W = d->win; a.C = d->cin; a.nc = split ? d->cin / 16 : d->cin / 32;      // K chunks: 64 bytes of a pixel's row
     a.relu = d->relu;
 #ifdef HMMR_GEMM_PROBE
-    a.ts = (unsigned long long*)(((unsigned long long)(unsigned)hmmr_debug_state()->reserved[1] << 32) | (unsigned)hmmr_debug_state()->reserved[0]);
+    a.ts = probe_stamp_buffer();
 #endif
     int tile = d->tile;
     const bool narrow = d->cout == 64, wide = d->win > 28;

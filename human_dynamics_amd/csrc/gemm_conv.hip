@@ -36,8 +36,7 @@
 #include <string.h>
 #include <type_traits>
 
-#include "common.h"
-#include "hmmr_hip.h"
+#include "stream_kit.h"
 
 struct ConvArgs {
     const void* in; const void* w; const float* scale; const float* shift;
@@ -134,9 +133,6 @@ template <typename TO> __device__ __forceinline__ void store_tail(TO* p, const f
 // 64 zero bytes in HBM: out-of-bounds gather slots of the LDS-DMA path read from here
 __device__ const u32x4 g_zero_page[4] = {};
 
-typedef const __attribute__((address_space(1))) void* gptr_t;
-typedef __attribute__((address_space(3))) void* lptr_t;
-
 // pre-activation of one 16-byte slot: relu(x * scale + shift) per element, back to the operand type
 template <typename TA> __device__ __forceinline__ u32x4 preact_slot(const u32x4& v, const f32x4* sc, const f32x4* sh);
 template <> __device__ __forceinline__ u32x4 preact_slot<float>(const u32x4& v, const f32x4* sc, const f32x4* sh) {
@@ -174,11 +170,7 @@ template <> __device__ __forceinline__ u32x4 preact_slot<bf16_t>(const u32x4& v,
 //         ResNet shape, with 4-wave 128x128, 8-wave 128x128 and 8-wave 256x128 tiles alike: it
 //         halves the resident workgroups per CU, and resident waves are what hides latency in this
 //         structure.
-// s_waitcnt with vmcnt = N, lgkmcnt = 0 (gfx9 encoding: vmcnt[3:0] | expcnt[6:4] | lgkmcnt[11:8] | vmcnt_hi[15:14])
-template <int N> __device__ __forceinline__ void wait_vm_lgkm0() {
-    static_assert(N >= 0 && N < 64, "vmcnt is a 6-bit counter");
-    __builtin_amdgcn_s_waitcnt((N & 15) | (7 << 4) | (0 << 8) | ((N >> 4) << 14));
-}
+// (counted waits: wait_vm_lgkm0<N> of stream_kit.h)
 
 // (A chunk-major K order for the 3x3 layers -- k' = (channel chunk, tap), so that the nine re-reads of a pixel's line fall
 //  into consecutive K steps -- was written in round 2 and measured in round 3: equal to rounding, 0 ... 3 % SLOWER on
@@ -1002,8 +994,8 @@ __global__ __launch_bounds__(512, 1) void conv3x3_pipe_kernel(const ConvArgs a) 
         t = t1; c = cn;
     };
     for (int kt = 0; kt < nk; kt += 2) {
-        step(std::integral_constant<int, 0>{}, kt);
-        if (kt + 1 < nk) step(std::integral_constant<int, 1>{}, kt + 1);
+        step(ic<0>{}, kt);
+        if (kt + 1 < nk) step(ic<1>{}, kt + 1);
     }
 
     patch_epilogue<TO, BM, BN, WGM, WGN>(a, smem, acc, m0, n0, tid, wm, wn, lr, lh);
@@ -1020,13 +1012,7 @@ static int launch_pipe(const ConvArgs& base, hipStream_t stream) {
     static_assert(lds <= 160 * 1024, "LDS");
     auto kern = conv3x3_pipe_kernel<TA, TO, NPP>;
     static DeviceOnce once;
-    if (const unsigned long long bit = once.due()) {
-        HMMR_CHECK_HIP(hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-        once.mark(bit);
-    }
-    hipLaunchKernelGGL(kern, dim3(a.n_tiles), dim3(512), lds, stream, a);
-    HMMR_CHECK_HIP(hipGetLastError());
-    return 0;
+    return launch_with_lds(kern, once, dim3(a.n_tiles), dim3(512), 160 * 1024, lds, stream, a);
 }
 
 // rows of the patch of a BM-row tile: its pixels, a halo of W + 1 on either side, and the two zero rows
@@ -1043,13 +1029,7 @@ static int launch_patch(const ConvArgs& base, hipStream_t stream) {
     static_assert(lds <= 160 * 1024, "LDS");
     auto kern = conv3x3_patch_kernel<TA, TO, BM, BN, WGM, WGN, NPP>;
     static DeviceOnce once;
-    if (const unsigned long long bit = once.due()) {
-        HMMR_CHECK_HIP(hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-        once.mark(bit);
-    }
-    hipLaunchKernelGGL(kern, dim3(a.n_tiles), dim3(512), lds, stream, a);
-    HMMR_CHECK_HIP(hipGetLastError());
-    return 0;
+    return launch_with_lds(kern, once, dim3(a.n_tiles), dim3(512), 160 * 1024, lds, stream, a);
 }
 
 template <typename TA, typename TO>
@@ -1091,17 +1071,10 @@ static int launch_cfg(const ConvArgs& base, int slices, hipStream_t stream) {
     if (lds > 160 * 1024) { hmmr_set_error("hmmr_conv_gemm: tile needs %d B of LDS (K = %d)", lds, a.K); return -1; }
     auto kern = conv_gemm_kernel<TA, TO, BM, BN, WGM, WGN, PRO, UTAP, NSTAGE>;
     static DeviceOnce once;              // per kernel instantiation, per device
-    if (const unsigned long long bit = once.due()) {
-        HMMR_CHECK_HIP(hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                           NSTAGE >= 3 ? 160 * 1024 : lds));
-        once.mark(bit);
-    }
     constexpr int BKE_ = 8 * elem_traits<TA>::EPS;
     const int nk = a.K / BKE_;
     a.kt_per_slice = (nk + slices - 1) / slices;
-    hipLaunchKernelGGL(kern, dim3(a.n_tiles, slices, a.batch), dim3(WGM * WGN * 64), lds, stream, a);
-    HMMR_CHECK_HIP(hipGetLastError());
-    return 0;
+    return launch_with_lds(kern, once, dim3(a.n_tiles, slices, a.batch), dim3(WGM * WGN * 64), NSTAGE >= 3 ? 160 * 1024 : lds, lds, stream, a);
 }
 
 template <typename TA, typename TO, bool PRO, bool UTAP>

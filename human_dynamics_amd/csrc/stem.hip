@@ -18,8 +18,7 @@
 #include <type_traits>
 #include <utility>
 
-#include "common.h"
-#include "hmmr_hip.h"
+#include "stream_kit.h"
 
 namespace {
 constexpr int IMG = 224, CONV = 112, POOL = 56, CO = 64;
@@ -355,31 +354,30 @@ __global__ __launch_bounds__(X3_NT) void stem_fused_split_kernel(const float* __
     // The 14 K steps (7 taps x 2 chunks of 16) with the six fragment reads of step s + 1 in flight under the six MFMAs of step s.
     // The reads are inline assembly: left to itself hipcc issues each step's reads right in front of their first use and waits for
     // them with the matrix pipe idle, 30 times per wave (round 4; per accumulator the order of the products is unchanged: same bits).
-    const unsigned lds0 = (unsigned)(unsigned long long)(__attribute__((address_space(3))) void*)smem;
+    const unsigned lds0 = lds_addr(smem);
     const unsigned aw = lds0 + 2 * X3_PLANE + bbase;            // filters: hi plane (+ X3_WPLANE: lo), + ky * 64 + c * 32
     unsigned ap[MPW];                                           // patch: hi plane (+ X3_PLANE: lo), + ky * IPW * 8 + c * 32
 #pragma unroll
     for (int i = 0; i < MPW; ++i) ap[i] = lds0 + abase[i];
     shalf8 fb[2][2], fa[2][MPW][2];                             // [set][...][hi, lo]
-#define STEM_RD(dst, addr, OFF) asm volatile("ds_read_b128 %0, %1 offset:%2" : "=v"(dst) : "v"(addr), "n"(OFF))
     auto load_step = [&](auto s_c, int set) {
         constexpr int S = decltype(s_c)::value, KY = S >> 1, C = S & 1;
         shalf8& bh = fb[set][0];
         shalf8& bl = fb[set][1];
-        STEM_RD(bh, aw, KY * 64 + C * 32);
-        STEM_RD(bl, aw, X3_WPLANE + KY * 64 + C * 32);
+        bh = lds_rd128<shalf8, KY * 64 + C * 32>(aw);
+        bl = lds_rd128<shalf8, X3_WPLANE + KY * 64 + C * 32>(aw);
 #pragma unroll
         for (int i = 0; i < MPW; ++i) {
             shalf8& ah = fa[set][i][0];
             shalf8& al = fa[set][i][1];
             const unsigned ad = ap[i];
-            STEM_RD(ah, ad, KY * IPW * 8 + C * 32);
-            STEM_RD(al, ad, X3_PLANE + KY * IPW * 8 + C * 32);
+            ah = lds_rd128<shalf8, KY * IPW * 8 + C * 32>(ad);
+            al = lds_rd128<shalf8, X3_PLANE + KY * IPW * 8 + C * 32>(ad);
         }
     };
     auto k_step = [&](auto s_c) {
         constexpr int S = decltype(s_c)::value, CUR = S & 1;
-        if constexpr (S + 1 < 14) load_step(std::integral_constant<int, (S + 1 < 14 ? S + 1 : 13)>{}, CUR ^ 1);
+        if constexpr (S + 1 < 14) load_step(ic<(S + 1 < 14 ? S + 1 : 13)>{}, CUR ^ 1);
 #pragma unroll
         for (int i = 0; i < MPW; ++i) {
             acc[i] = mfma_split(fa[CUR][i][1], fb[CUR][0], acc[i]);
@@ -387,18 +385,14 @@ __global__ __launch_bounds__(X3_NT) void stem_fused_split_kernel(const float* __
             acc[i] = mfma_split(fa[CUR][i][0], fb[CUR][0], acc[i]);
         }
         __builtin_amdgcn_sched_barrier(0);
-        __builtin_amdgcn_s_waitcnt(63 | (7 << 4) | (0 << 8) | (3 << 14));      // lgkmcnt(0): the next step's fragments
+        wait_lgkm<0>();                               // the next step's fragments
         __builtin_amdgcn_sched_barrier(0);
     };
-    load_step(std::integral_constant<int, 0>{}, 0);
-    __builtin_amdgcn_s_waitcnt(63 | (7 << 4) | (0 << 8) | (3 << 14));
+    load_step(ic<0>{}, 0);
+    wait_lgkm<0>();
     __builtin_amdgcn_sched_barrier(0);
     auto k_steps = [&](auto... S) { (k_step(S), ...); };
-    k_steps(std::integral_constant<int, 0>{}, std::integral_constant<int, 1>{}, std::integral_constant<int, 2>{}, std::integral_constant<int, 3>{},
-            std::integral_constant<int, 4>{}, std::integral_constant<int, 5>{}, std::integral_constant<int, 6>{}, std::integral_constant<int, 7>{},
-            std::integral_constant<int, 8>{}, std::integral_constant<int, 9>{}, std::integral_constant<int, 10>{}, std::integral_constant<int, 11>{},
-            std::integral_constant<int, 12>{}, std::integral_constant<int, 13>{});
-#undef STEM_RD
+    k_steps(ic<0>{}, ic<1>{}, ic<2>{}, ic<3>{}, ic<4>{}, ic<5>{}, ic<6>{}, ic<7>{}, ic<8>{}, ic<9>{}, ic<10>{}, ic<11>{}, ic<12>{}, ic<13>{});
     __syncthreads();                              // every wave is done with the filters: reuse as staging
 
     // ---- 4a. conv + bias, rounded to what split storage holds, -> LDS fp32 [pixel][32]
@@ -507,36 +501,18 @@ int hmmr_stem_fused(const float* images, int n_real, int n, const void* wts, con
                     const float* pscale, const float* pshift, void* out, int dtype, hipStream_t s,
                     const void* w1, const float* s1, const float* b1, void* out_h1) {
     if (dtype == HMMR_F16X3) {
-        auto kern = stem_fused_split_kernel;
         static DeviceOnce oncex3;
-        if (const unsigned long long bit = oncex3.due()) {
-            HMMR_CHECK_HIP(hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, X3_LDS));
-            oncex3.mark(bit);
-        }
-        hipLaunchKernelGGL(kern, dim3((POOL / PT) * (POOL / PT), n), dim3(X3_NT), X3_LDS, s, images,
-                           (const bsplit_t*)wts, wscale, bias, pscale, pshift, (bsplit_t*)out, n_real, (const char*)w1, s1, b1,
-                           (bsplit_t*)out_h1);
+        return launch_with_lds(stem_fused_split_kernel, oncex3, dim3((POOL / PT) * (POOL / PT), n), dim3(X3_NT), X3_LDS, X3_LDS, s, images,
+                               (const bsplit_t*)wts, wscale, bias, pscale, pshift, (bsplit_t*)out, n_real, (const char*)w1, s1, b1,
+                               (bsplit_t*)out_h1);
     } else if (dtype == HMMR_BF16) {
-        auto kern = stem_fused_kernel<bf16_t>;
         static DeviceOnce once16;
-        if (const unsigned long long bit = once16.due()) {
-            HMMR_CHECK_HIP(hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, StemLds<bf16_t>::TOTAL));
-            once16.mark(bit);
-        }
-        hipLaunchKernelGGL(kern, dim3((POOL / PT) * (POOL / PT), n), dim3(256), StemLds<bf16_t>::TOTAL, s, images,
-                           (const bf16_t*)wts, bias, pscale, pshift, (bf16_t*)out, n_real, (const bf16_t*)w1, s1, b1,
-                           (bf16_t*)out_h1);
-    } else {
-        auto kern = stem_fused_kernel<float>;
-        static DeviceOnce once32;
-        if (const unsigned long long bit = once32.due()) {
-            HMMR_CHECK_HIP(hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, StemLds<float>::TOTAL));
-            once32.mark(bit);
-        }
-        hipLaunchKernelGGL(kern, dim3((POOL / PT) * (POOL / PT), n), dim3(256), StemLds<float>::TOTAL, s, images,
-                           (const float*)wts, bias, pscale, pshift, (float*)out, n_real, (const float*)nullptr,
-                           (const float*)nullptr, (const float*)nullptr, (float*)nullptr);
+        return launch_with_lds(stem_fused_kernel<bf16_t>, once16, dim3((POOL / PT) * (POOL / PT), n), dim3(256), StemLds<bf16_t>::TOTAL,
+                               StemLds<bf16_t>::TOTAL, s, images, (const bf16_t*)wts, bias, pscale, pshift, (bf16_t*)out, n_real,
+                               (const bf16_t*)w1, s1, b1, (bf16_t*)out_h1);
     }
-    HMMR_CHECK_HIP(hipGetLastError());
-    return 0;
+    static DeviceOnce once32;
+    return launch_with_lds(stem_fused_kernel<float>, once32, dim3((POOL / PT) * (POOL / PT), n), dim3(256), StemLds<float>::TOTAL,
+                           StemLds<float>::TOTAL, s, images, (const float*)wts, bias, pscale, pshift, (float*)out, n_real,
+                           (const float*)nullptr, (const float*)nullptr, (const float*)nullptr, (float*)nullptr);
 }

@@ -36,19 +36,11 @@
 // Every wave executes the same sequence of vector-memory instructions (invalid rows read row 0 and store to a dump page),
 // so the waits on the ring are COUNTED s_waitcnt vmcnt(N) with N a compile-time function of the position in the
 // iteration.
-#include <type_traits>
-
-#include "common.h"
-#include "hmmr_hip.h"
+#include "stream_kit.h"
 
 namespace {
 
-typedef const __attribute__((address_space(1))) void* gptr_t;
-typedef __attribute__((address_space(3))) void* lptr_t;
 typedef __attribute__((ext_vector_type(2))) unsigned u32x2;
-typedef __attribute__((ext_vector_type(2))) _Float16 shalf2_t;
-
-__device__ u32x4 g_pair_dump[64];          // 1 KB: where the stores of rows beyond M (and of the pipeline's fill / drain iterations) go
 
 struct PairArgs {
     const bsplit_t* src[2]; int src_ld[2];  // conv3's K: KC3A 16-wide chunks from rows of src[0], KC3B from rows of src[1] (row strides in elements)
@@ -95,11 +87,6 @@ __host__ __device__ constexpr int pair_wait_n(int p, int cl, int ns, int eops) {
     return n;
 }
 
-// s_waitcnt vmcnt(N) alone (gfx9 encoding: vmcnt[3:0] | expcnt[6:4] | lgkmcnt[11:8] | vmcnt_hi[15:14])
-template <int N> __device__ __forceinline__ void wait_vm() {
-    static_assert(N >= 0 && N < 64, "vmcnt is a 6-bit counter");
-    __builtin_amdgcn_s_waitcnt((N & 15) | (7 << 4) | (15 << 8) | ((N >> 4) << 14));
-}
 template <int CL, int NS, int EOPS> __device__ __forceinline__ void wait_pos(int p) {      // p is a constant after unrolling
     if (p == 0) wait_vm<pair_wait_n(0, CL, NS, EOPS)>();
     if constexpr (CL > 1) { if (p == 1) wait_vm<pair_wait_n(1, CL, NS, EOPS)>(); }
@@ -110,27 +97,11 @@ template <int CL, int NS, int EOPS> __device__ __forceinline__ void wait_pos(int
     static_assert(CL <= 6, "at most 6 slabs per iteration");
 }
 
-struct xfrag { shalf8 hi, lo; };            // MFMA B-operand fragment of 32 pixels x 16 channels
-
-// LDS accesses of the loop as inline assembly.  hipcc waits lgkmcnt(0) wherever LDS data is first used -- never a counted wait -- which
-// drains this unit's fragment requests whenever an older value is touched (~100 cycles with the matrix pipe idle, every unit: profiles/
-// r04a).  These the compiler does not track: the loop places its own COUNTED waits (LDS operations of a wave complete in order).
-template <int OFF> __device__ __forceinline__ shalf8 lds_rd128h(unsigned addr) {
-    shalf8 v; asm volatile("ds_read_b128 %0, %1 offset:%2" : "=v"(v) : "v"(addr), "n"(OFF)); return v;
-}
-template <int OFF> __device__ __forceinline__ f32x4 lds_rd128f(unsigned addr) {
-    f32x4 v; asm volatile("ds_read_b128 %0, %1 offset:%2" : "=v"(v) : "v"(addr), "n"(OFF)); return v;
-}
-template <int OFF> __device__ __forceinline__ unsigned long long lds_rd64(unsigned addr) {
-    unsigned long long v; asm volatile("ds_read_b64 %0, %1 offset:%2" : "=v"(v) : "v"(addr), "n"(OFF)); return v;
-}
-template <int OFF> __device__ __forceinline__ void lds_wr64(unsigned addr, unsigned long long v) {
-    asm volatile("ds_write_b64 %0, %1 offset:%2" : : "v"(addr), "v"(v), "n"(OFF) : "memory");
-}
+// (the loops' LDS accesses are lds_rd128 / lds_rd64 / lds_wr64 of stream_kit.h: the loops place their own COUNTED waits)
 // fragment f (0..7) of the slab at LDS address `base` (already + 16 * lane): hi plane, lo plane
 __device__ __forceinline__ wfrag lds_frag(unsigned base, int f) {      // f is a constant after unrolling
     wfrag w;
-#define PAIR_F(k) if (f == k) { w.hi = lds_rd128h<k * 2048>(base); w.lo = lds_rd128h<k * 2048 + 1024>(base); }
+#define PAIR_F(k) if (f == k) { w.hi = lds_rd128<shalf8, k * 2048>(base); w.lo = lds_rd128<shalf8, k * 2048 + 1024>(base); }
     PAIR_F(0) PAIR_F(1) PAIR_F(2) PAIR_F(3) PAIR_F(4) PAIR_F(5) PAIR_F(6) PAIR_F(7)
 #undef PAIR_F
     return w;
@@ -138,14 +109,14 @@ __device__ __forceinline__ wfrag lds_frag(unsigned base, int f) {      // f is a
 // one plane (h: 0 = hi, 1 = lo) of fragment f
 __device__ __forceinline__ shalf8 lds_frag_half(unsigned base, int f, int h) {
     shalf8 v = {};
-#define PAIR_F(k) if (f == k) { if (h == 0) v = lds_rd128h<k * 2048>(base); else v = lds_rd128h<k * 2048 + 1024>(base); }
+#define PAIR_F(k) if (f == k) { if (h == 0) v = lds_rd128<shalf8, k * 2048>(base); else v = lds_rd128<shalf8, k * 2048 + 1024>(base); }
     PAIR_F(0) PAIR_F(1) PAIR_F(2) PAIR_F(3) PAIR_F(4) PAIR_F(5) PAIR_F(6) PAIR_F(7)
 #undef PAIR_F
     return v;
 }
 // s_waitcnt lgkmcnt(n) alone, n a constant after unrolling
-__device__ __forceinline__ void wait_lgkm(int n) {
-#define PAIR_W(k) if (n == k) __builtin_amdgcn_s_waitcnt((63 & 15) | (7 << 4) | (k << 8) | ((63 >> 4) << 14));
+__device__ __forceinline__ void wait_lgkm_n(int n) {
+#define PAIR_W(k) if (n == k) wait_lgkm<k>();
     PAIR_W(0) PAIR_W(1) PAIR_W(2) PAIR_W(3) PAIR_W(4) PAIR_W(5) PAIR_W(6) PAIR_W(7) PAIR_W(8) PAIR_W(9) PAIR_W(10) PAIR_W(11) PAIR_W(12)
     PAIR_W(13) PAIR_W(14) PAIR_W(15)
 #undef PAIR_W
@@ -303,7 +274,7 @@ __global__ __launch_bounds__(256, 1) void unit_pair_kernel(const PairArgs a) {
     PAIR_STAMP(2);
 
     const int lane16 = lane * 16;
-    const unsigned lds0 = (unsigned)(unsigned long long)(lptr_t)smem;      // LDS byte address of smem (0 unless something is linked in front)
+    const unsigned lds0 = lds_addr(smem);      // LDS byte address of smem (0 unless something is linked in front)
     const int sw = (lr >> 1) & 7;
     const float one = a.one;                                   // 1.0f the compiler cannot fold: fma(h, one, l) is ONE v_fma_mix_f32
     // row pieces of the staging tile <-> global rows: piece q = rows 8q + rsub, this lane's 16 bytes = logical slot ls of the row
@@ -317,7 +288,7 @@ __global__ __launch_bounds__(256, 1) void unit_pair_kernel(const PairArgs a) {
         const int r = 8 * q + rsub, m = mbase + r;
         const int ls = pslot ^ ((r >> 1) & 7);
         const bool ok = m < a.M;
-        orow[q] = ok ? a.out + (long long)m * DEPTH + ls * 4 : (bsplit_t*)g_pair_dump + lane * 4;
+        orow[q] = ok ? a.out + (long long)m * DEPTH + ls * 4 : (bsplit_t*)g_dump_page + lane * 4;
         ostep[q] = ok ? 32 : 0;
         if constexpr (RES) rrow[q] = a.res + (long long)(ok ? m : 0) * a.ldr + ls * 4 + 32;
     }
@@ -338,7 +309,7 @@ __global__ __launch_bounds__(256, 1) void unit_pair_kernel(const PairArgs a) {
 #pragma unroll
     for (int g = 0; g < 4; ++g)
 #pragma unroll
-        for (int pl = 0; pl < 2; ++pl) soff[g][pl] = lds0 + OFF_STG + wave * 8192 + lr * 128 + (((2 * g + pl) ^ sw) << 4) + 8 * lh;
+        for (int pl = 0; pl < 2; ++pl) soff[g][pl] = stage_slot(lds0 + OFF_STG + wave * 8192, lr, lh, g, sw, pl);
 
     // what the epilogue of a chunk reads out of LDS (its constants, the shortcut chunk), per group of 8 channels
     f32x4 cs3[4], cb3[4], cps[4], cpb[4];
@@ -349,10 +320,10 @@ __global__ __launch_bounds__(256, 1) void unit_pair_kernel(const PairArgs a) {
         const int ec_ = e_ < 0 ? 0 : (e_ >= NCH ? NCH - 1 : e_);
         const unsigned cb = cbase0 + ec_ * 128;
 #define PAIR_G(k) if (g == k) { \
-            if (j == 0) cs3[k] = lds_rd128f<k * 32>(cb); \
-            if (j == 1) cb3[k] = lds_rd128f<k * 32 + DEPTH * 4>(cb); \
-            if (j == 2) cps[k] = lds_rd128f<k * 32 + DEPTH * 8>(cb); \
-            if (j == 3) cpb[k] = lds_rd128f<k * 32 + DEPTH * 12>(cb); \
+            if (j == 0) cs3[k] = lds_rd128<f32x4, k * 32>(cb); \
+            if (j == 1) cb3[k] = lds_rd128<f32x4, k * 32 + DEPTH * 4>(cb); \
+            if (j == 2) cps[k] = lds_rd128<f32x4, k * 32 + DEPTH * 8>(cb); \
+            if (j == 3) cpb[k] = lds_rd128<f32x4, k * 32 + DEPTH * 12>(cb); \
             if constexpr (RES) { if (j == 4) rh[k] = lds_rd64<B * 4096>(soff[k][0]); if (j == 5) rl[k] = lds_rd64<B * 4096>(soff[k][1]); } }
         PAIR_G(0) PAIR_G(1) PAIR_G(2) PAIR_G(3)
 #undef PAIR_G
@@ -378,8 +349,8 @@ __global__ __launch_bounds__(256, 1) void unit_pair_kernel(const PairArgs a) {
     wfrag wq[4][2];                                            // fragments of the units u, u+1, u+2 (slot u & 3): requested TWO units ahead
 #pragma unroll
     for (int u = 0; u < 2; ++u) { wq[u][0] = lds_frag(fbase0 + slot * SLAB, 2 * u); wq[u][1] = lds_frag(fbase0 + slot * SLAB, 2 * u + 1); }
-    group_loads(-1, std::integral_constant<int, 1>{}, 0);
-    wait_lgkm(0);
+    group_loads(-1, ic<1>{}, 0);
+    wait_lgkm_n(0);
     __builtin_amdgcn_sched_barrier(0);
 
     // One iteration: the MFMAs of conv3 chunk `it` (-> accN) and of conv1' K step it - 2 (-> acc2), the epilogue of chunk it - 1
@@ -467,7 +438,7 @@ __global__ __launch_bounds__(256, 1) void unit_pair_kernel(const PairArgs a) {
                 // first piece, that group's reads (LDU units ago).  Issued since, and allowed to stay in flight: the writes of
                 // unit uu - 2 (LDU 2) and all of unit uu - 1.
                 __builtin_amdgcn_sched_barrier(0);
-                wait_lgkm((LDU == 2 ? n_c(uu - 2) + 4 + n_b(uu - 1) : 0) + n_c(uu - 1));
+                wait_lgkm_n((LDU == 2 ? n_c(uu - 2) + 4 + n_b(uu - 1) : 0) + n_c(uu - 1));
                 __builtin_amdgcn_sched_barrier(0);
                 const wfrag w0 = wq[uu & 3][0], w1 = wq[uu & 3][1];
                 const bool a0 = pair_is_a(i0, NA, FT), a1 = pair_is_a(i1, NA, FT);
@@ -514,9 +485,9 @@ __global__ __launch_bounds__(256, 1) void unit_pair_kernel(const PairArgs a) {
                         // group 0 of the NEXT iteration's epilogue: the shortcut chunk `it` was requested at the end of iteration
                         // it - 1, and this wave has issued the 4 CL slab requests of this iteration since (in-order completion)
                         if (RES && j == 4) wait_vm<4 * CL>();
-                        group_load(it, std::integral_constant<int, PAR>{}, 0, j);
+                        group_load(it, ic<PAR>{}, 0, j);
                     } else {
-                        group_load(e, std::integral_constant<int, BE>{}, glg, j);
+                        group_load(e, ic<BE>{}, glg, j);
                     }
                 };
                 // one MFMA, then this gap's share of the reads (a ds_read_b128 holds the wave's LDS port for 16 cycles: more than two
@@ -572,7 +543,7 @@ __global__ __launch_bounds__(256, 1) void unit_pair_kernel(const PairArgs a) {
             for (int q = 0; q < 4; ++q) { *(u32x4*)orow[q] = xr[q]; orow[q] += ostep[q]; }
         } else {
 #pragma unroll
-            for (int q = 0; q < 4; ++q) *(u32x4*)((bsplit_t*)g_pair_dump + lane * 4) = xr[q];
+            for (int q = 0; q < 4; ++q) *(u32x4*)((bsplit_t*)g_dump_page + lane * 4) = xr[q];
         }
         if constexpr (RES) {
             // chunk e + 2 (the last two iterations re-request the last chunk: harmless, and the instruction count stays uniform)
@@ -590,8 +561,8 @@ __global__ __launch_bounds__(256, 1) void unit_pair_kernel(const PairArgs a) {
 #pragma unroll
     for (int r = 0; r < 16; ++r) accB[r] = 0.f;
     for (int it = 0; it <= NCH + 1; it += 2) {
-        iteration(it, std::integral_constant<int, 0>{}, acc1, accB);
-        iteration(it + 1, std::integral_constant<int, 1>{}, accB, acc1);
+        iteration(it, ic<0>{}, acc1, accB);
+        iteration(it + 1, ic<1>{}, accB, acc1);
     }
 
     // ---- conv1' epilogue: BN (+ ReLU), split, through this wave's staging tile, coalesced stores
@@ -629,7 +600,7 @@ __global__ __launch_bounds__(256, 1) void unit_pair_kernel(const PairArgs a) {
     for (int q = 0; q < 4; ++q) {
         const int r = 8 * q + rsub, m = mbase + r;
         const int ls = pslot ^ ((r >> 1) & 7);
-        hrow[q] = m < a.M ? a.out_h1 + (long long)m * N2 + ls * 4 : (bsplit_t*)g_pair_dump + lane * 4;
+        hrow[q] = m < a.M ? a.out_h1 + (long long)m * N2 + ls * 4 : (bsplit_t*)g_dump_page + lane * 4;
     }
 #pragma unroll
     for (int of = 0; of < NF2; ++of) {
@@ -644,8 +615,7 @@ __global__ __launch_bounds__(256, 1) void unit_pair_kernel(const PairArgs a) {
             //  instruction count -- this epilogue is 128 values per lane in block 3 with nothing to hide behind)
             unsigned h2[2], l2[2];
             split4_mix(v, lo1, h2, l2, satmax);
-            *(unsigned long long*)(stg + (of & 1) * 4096 + lr * 128 + (((2 * g) ^ sw) << 4) + 8 * lh) = (unsigned long long)h2[0] | ((unsigned long long)h2[1] << 32);
-            *(unsigned long long*)(stg + (of & 1) * 4096 + lr * 128 + (((2 * g + 1) ^ sw) << 4) + 8 * lh) = (unsigned long long)l2[0] | ((unsigned long long)l2[1] << 32);
+            stage_store_group(stg + (of & 1) * 4096, lr, lh, g, sw, h2, l2);
         }
         // (the two staging tiles alternate: the row reads of block `of` do not hold up the writes of block of + 1)
         u32x4 xr[4];
@@ -763,18 +733,11 @@ __host__ __device__ constexpr int wsb_wait(int u, int nb) {
 }
 // the wait of unit u (a constant after unrolling) with its count as a template argument: left as a function of a run-time-typed u the
 // compiler evaluates the counting loops at RUN time and switches over the sixteen encodings
-template <int N> __device__ __forceinline__ void wait_lgkm_c() {
-    static_assert(N >= 0 && N <= 15, "lgkmcnt is a 4-bit counter");
-    __builtin_amdgcn_s_waitcnt((63 & 15) | (7 << 4) | (N << 8) | ((63 >> 4) << 14));
-}
 template <int NU, bool IS_A> __device__ __forceinline__ void ws_wait_unit(int u) {
-#define WS_WU(k) if constexpr (NU > k) { if (u == k) wait_lgkm_c<IS_A ? wsa_wait(k, NU) : wsb_wait(k, NU)>(); }
+#define WS_WU(k) if constexpr (NU > k) { if (u == k) wait_lgkm<IS_A ? wsa_wait(k, NU) : wsb_wait(k, NU)>(); }
     WS_WU(0) WS_WU(1) WS_WU(2) WS_WU(3) WS_WU(4) WS_WU(5) WS_WU(6) WS_WU(7) WS_WU(8) WS_WU(9) WS_WU(10) WS_WU(11) WS_WU(12) WS_WU(13) WS_WU(14) WS_WU(15)
 #undef WS_WU
     static_assert(NU <= 16, "at most 16 units per iteration");
-}
-template <int OFF> __device__ __forceinline__ u32x4 lds_rd128u(unsigned addr) {
-    u32x4 v; asm volatile("ds_read_b128 %0, %1 offset:%2" : "=v"(v) : "v"(addr), "n"(OFF)); return v;
 }
 
 // probe build (tools/pair_probe_build.sh): s_memtime stamps [blocks][8 waves][8] -- 0 start, 1 in front of the prologue's wait, 2 loop entry, 3 loop
@@ -819,7 +782,7 @@ __global__ __launch_bounds__(512, 1) void unit_pair_ws_kernel(const PairArgs a) 
     const bool roleB = wave >= 4;
     const int lr = lane & 31, lh = lane >> 5;
     const int mbase = blockIdx.x * 128 + pr * 32;
-    const unsigned lds0 = (unsigned)(unsigned long long)(lptr_t)smem;
+    const unsigned lds0 = lds_addr(smem);
     const int lane16 = lane * 16;
     const int sw = (lr >> 1) & 7;
 
@@ -886,7 +849,7 @@ __global__ __launch_bounds__(512, 1) void unit_pair_ws_kernel(const PairArgs a) 
 #pragma unroll
         for (int g = 0; g < 4; ++g)
 #pragma unroll
-            for (int pl = 0; pl < 2; ++pl) soff[g][pl] = tile0 + lr * 128 + (((2 * g + pl) ^ sw) << 4) + 8 * lh;
+            for (int pl = 0; pl < 2; ++pl) soff[g][pl] = stage_slot(tile0, lr, lh, g, sw, pl);
         const unsigned cbase0 = lds0 + OFF_C + lh * 16;        // + chunk * 128 (+ g * 32): scale3; shift3 at + DEPTH * 4
 
         wfrag wq[4];                                           // fragment of unit u in wq[u & 3], requested WS_PF units ahead
@@ -910,7 +873,7 @@ __global__ __launch_bounds__(512, 1) void unit_pair_ws_kernel(const PairArgs a) 
 #pragma unroll
             for (int p = 0; p < CL; ++p) {
                 __builtin_amdgcn_sched_barrier(0);
-                if (p == 0) wait_lgkm(0);                      // this wave's trunk writes of the last iteration: B reads them behind this barrier
+                if (p == 0) wait_lgkm_n(0);                      // this wave's trunk writes of the last iteration: B reads them behind this barrier
                 if (!PAIR_PROBE(a, 4)) __builtin_amdgcn_s_barrier();
                 __builtin_amdgcn_sched_barrier(0);
                 const int nslot = slot + 1 == NS ? 0 : slot + 1;
@@ -924,13 +887,13 @@ __global__ __launch_bounds__(512, 1) void unit_pair_ws_kernel(const PairArgs a) 
                     const int gl = (ua % U4 == 0) ? ua / U4 : -1;
                     if (gl >= 0 && !PAIR_PROBE(a, 8)) {
 #define WS_GL(k) if (gl == k) { \
-                            cs3v = lds_rd128f<k * 32>(cb); cb3v = lds_rd128f<k * 32 + DEPTH * 4>(cb); \
+                            cs3v = lds_rd128<f32x4, k * 32>(cb); cb3v = lds_rd128<f32x4, k * 32 + DEPTH * 4>(cb); \
                             rhv = lds_rd64<0>(soff[k][0] + toff); rlv = lds_rd64<0>(soff[k][1] + toff); }
                         WS_GL(0) WS_GL(1) WS_GL(2) WS_GL(3)
 #undef WS_GL
                     }
                     __builtin_amdgcn_sched_barrier(0);
-                    if (PAIR_PROBE(a, 32) || PAIR_PROBE(a, 8)) wait_lgkm(0); else if (!PAIR_PROBE(a, 128)) ws_wait_unit<NA, true>(ua);
+                    if (PAIR_PROBE(a, 32) || PAIR_PROBE(a, 8)) wait_lgkm_n(0); else if (!PAIR_PROBE(a, 128)) ws_wait_unit<NA, true>(ua);
                     __builtin_amdgcn_sched_barrier(0);
                     // (past the last chunk the stream holds zero fragments: the MFMAs run on them rather than behind a branch per unit)
                     if (!PAIR_PROBE(a, 1) && !PAIR_PROBE(a, 512)) {
@@ -985,7 +948,7 @@ __global__ __launch_bounds__(512, 1) void unit_pair_ws_kernel(const PairArgs a) 
             // the next iteration's first fragments are in flight into registers the compiler knows nothing asynchronous about: let them
             // land before anything (a loop-carried copy) may touch them
             __builtin_amdgcn_sched_barrier(0);
-            wait_lgkm(0);
+            wait_lgkm_n(0);
             __builtin_amdgcn_sched_barrier(0);
         };
         for (int it = 0; it <= NCH + 1; it += 2) {
@@ -1020,7 +983,7 @@ __global__ __launch_bounds__(512, 1) void unit_pair_ws_kernel(const PairArgs a) 
         const int r = 8 * q + rsub, m = mbase + r;
         const int ls = pslot ^ ((r >> 1) & 7);
         const bool ok = m < a.M;
-        orow[q] = ok ? a.out + (long long)m * DEPTH + ls * 4 : (bsplit_t*)g_pair_dump + lane * 4;
+        orow[q] = ok ? a.out + (long long)m * DEPTH + ls * 4 : (bsplit_t*)g_dump_page + lane * 4;
         ostep[q] = ok ? 32 : 0;
         rrow[q] = a.res + (long long)(ok ? m : 0) * a.ldr + ls * 4;
     }
@@ -1115,23 +1078,23 @@ __global__ __launch_bounds__(512, 1) void unit_pair_ws_kernel(const PairArgs a) 
                 if (!PAIR_PROBE(a, 16)) {
                     if (ub == 0) {                             // K chunk 1 of the finished tile (chunk it - 2): operand slots + constants
                         const unsigned pb_ = pbase0 + e2c * 128;
-                        rawh = lds_rd128u<0>(toffB[1][0] + toff); rawl = lds_rd128u<0>(toffB[1][1] + toff);
-                        psv[0] = lds_rd128f<64>(pb_); psv[1] = lds_rd128f<64 + 16>(pb_);
-                        pbv[0] = lds_rd128f<DEPTH * 4 + 64>(pb_); pbv[1] = lds_rd128f<DEPTH * 4 + 64 + 16>(pb_);
+                        rawh = lds_rd128<u32x4, 0>(toffB[1][0] + toff); rawl = lds_rd128<u32x4, 0>(toffB[1][1] + toff);
+                        psv[0] = lds_rd128<f32x4, 64>(pb_); psv[1] = lds_rd128<f32x4, 64 + 16>(pb_);
+                        pbv[0] = lds_rd128<f32x4, DEPTH * 4 + 64>(pb_); pbv[1] = lds_rd128<f32x4, DEPTH * 4 + 64 + 16>(pb_);
                     }
                     if (ub == 1) {                             // its rows
-                        xr[0] = lds_rd128u<0>(tile0 + toff + lane16); xr[1] = lds_rd128u<1024>(tile0 + toff + lane16);
-                        xr[2] = lds_rd128u<2048>(tile0 + toff + lane16); xr[3] = lds_rd128u<3072>(tile0 + toff + lane16);
+                        xr[0] = lds_rd128<u32x4, 0>(tile0 + toff + lane16); xr[1] = lds_rd128<u32x4, 1024>(tile0 + toff + lane16);
+                        xr[2] = lds_rd128<u32x4, 2048>(tile0 + toff + lane16); xr[3] = lds_rd128<u32x4, 3072>(tile0 + toff + lane16);
                     }
                     if (ub == H) {                             // K chunk 0 of the tile wave A is half way through (chunk it - 1: its groups 0, 1 are written)
                         const unsigned pb_ = pbase0 + e1c * 128;
-                        rawh = lds_rd128u<0>(toffB[0][0] + toff1); rawl = lds_rd128u<0>(toffB[0][1] + toff1);
-                        psv[0] = lds_rd128f<0>(pb_); psv[1] = lds_rd128f<16>(pb_);
-                        pbv[0] = lds_rd128f<DEPTH * 4>(pb_); pbv[1] = lds_rd128f<DEPTH * 4 + 16>(pb_);
+                        rawh = lds_rd128<u32x4, 0>(toffB[0][0] + toff1); rawl = lds_rd128<u32x4, 0>(toffB[0][1] + toff1);
+                        psv[0] = lds_rd128<f32x4, 0>(pb_); psv[1] = lds_rd128<f32x4, 16>(pb_);
+                        pbv[0] = lds_rd128<f32x4, DEPTH * 4>(pb_); pbv[1] = lds_rd128<f32x4, DEPTH * 4 + 16>(pb_);
                     }
                 }
                 __builtin_amdgcn_sched_barrier(0);
-                if (PAIR_PROBE(a, 32) || PAIR_PROBE(a, 16)) wait_lgkm(0); else if (!PAIR_PROBE(a, 256)) ws_wait_unit<NB, false>(ub);
+                if (PAIR_PROBE(a, 32) || PAIR_PROBE(a, 16)) wait_lgkm_n(0); else if (!PAIR_PROBE(a, 256)) ws_wait_unit<NB, false>(ub);
                 __builtin_amdgcn_sched_barrier(0);
                 if (!PAIR_PROBE(a, 1) && !PAIR_PROBE(a, 1024)) {       // (iterations 0, 1: zero fragments in the stream)
                     const wfrag& w = wq[ub & 3];
@@ -1158,7 +1121,7 @@ __global__ __launch_bounds__(512, 1) void unit_pair_ws_kernel(const PairArgs a) 
                             for (int q = 0; q < 4; ++q) { *(u32x4*)orow[q] = xr[q]; orow[q] += ostep[q]; }
                         } else {
 #pragma unroll
-                            for (int q = 0; q < 4; ++q) *(u32x4*)((bsplit_t*)g_pair_dump + lane * 4) = xr[q];
+                            for (int q = 0; q < 4; ++q) *(u32x4*)((bsplit_t*)g_dump_page + lane * 4) = xr[q];
                         }
                         dma_res(tilep + toff, 0);               // shortcut chunk it + 1 (past the end: the last chunk again)
                         if (it + 2 < NCH) {
@@ -1180,7 +1143,7 @@ __global__ __launch_bounds__(512, 1) void unit_pair_ws_kernel(const PairArgs a) 
             slot = nslot;
         }
         __builtin_amdgcn_sched_barrier(0);
-        wait_lgkm(0);                                           // (the prefetched fragments: see wave A)
+        wait_lgkm_n(0);                                           // (the prefetched fragments: see wave A)
         __builtin_amdgcn_sched_barrier(0);
     }
 
@@ -1199,7 +1162,7 @@ __global__ __launch_bounds__(512, 1) void unit_pair_ws_kernel(const PairArgs a) 
     for (int q = 0; q < 4; ++q) {
         const int r = 8 * q + rsub, m = mbase + r;
         const int ls = pslot ^ ((r >> 1) & 7);
-        hrow[q] = m < a.M ? a.out_h1 + (long long)m * N2 + ls * 4 : (bsplit_t*)g_pair_dump + lane * 4;
+        hrow[q] = m < a.M ? a.out_h1 + (long long)m * N2 + ls * 4 : (bsplit_t*)g_dump_page + lane * 4;
     }
 #pragma unroll
     for (int of = 0; of < NF2; ++of) {
@@ -1212,8 +1175,7 @@ __global__ __launch_bounds__(512, 1) void unit_pair_ws_kernel(const PairArgs a) 
             for (int j = 0; j < 4; ++j) v[j] = fmaf(acc2[of][4 * g + j], s4[j], b4[j]);
             unsigned h2[2], l2[2];
             split4_mix(v, lo1, h2, l2, satmax);
-            *(unsigned long long*)(tilep + (of & 1) * 4096 + lr * 128 + (((2 * g) ^ sw) << 4) + 8 * lh) = (unsigned long long)h2[0] | ((unsigned long long)h2[1] << 32);
-            *(unsigned long long*)(tilep + (of & 1) * 4096 + lr * 128 + (((2 * g + 1) ^ sw) << 4) + 8 * lh) = (unsigned long long)l2[0] | ((unsigned long long)l2[1] << 32);
+            stage_store_group(tilep + (of & 1) * 4096, lr, lh, g, sw, h2, l2);
         }
         u32x4 xr[4];
 #pragma unroll
@@ -1236,15 +1198,9 @@ int launch_pair_ws(const PairArgs& a, hipStream_t stream) {
     static_assert(lds <= 160 * 1024, "LDS");
     auto kern = unit_pair_ws_kernel<KC3, DEPTH, N2>;
     static DeviceOnce once;
-    if (const unsigned long long bit = once.due()) {
-        HMMR_CHECK_HIP(hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, lds));
-        once.mark(bit);
-    }
     PairArgs b = a;
     b.tpw = 1;
-    hipLaunchKernelGGL(kern, dim3((unsigned)((a.M + 127) / 128)), dim3(512), lds, stream, b);
-    HMMR_CHECK_HIP(hipGetLastError());
-    return 0;
+    return launch_with_lds(kern, once, dim3((unsigned)((a.M + 127) / 128)), dim3(512), lds, lds, stream, b);
 }
 
 template <int KC3A, int KC3B, int DEPTH, int N2, bool RES>
@@ -1253,10 +1209,6 @@ int launch_pair(const PairArgs& a, hipStream_t stream) {
     static_assert(lds <= 160 * 1024, "LDS");
     auto kern = unit_pair_kernel<KC3A, KC3B, DEPTH, N2, RES>;
     static DeviceOnce once;
-    if (const unsigned long long bit = once.due()) {
-        HMMR_CHECK_HIP(hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, lds));
-        once.mark(bit);
-    }
     // persistent workgroups (block-2 shapes) once the launch is at least two rounds of one workgroup per CU: below that a second tile only
     // lengthens the launch (hmmr_debug_t.pair_two_tile_min moves the switch: tests run both forms on one batch)
     PairArgs b = a;
@@ -1269,9 +1221,7 @@ int launch_pair(const PairArgs& a, hipStream_t stream) {
         grid = n_tiles < cus ? (n_tiles + 1) / 2 : cus;          // (forced on for a short launch: two tiles per workgroup)
         b.tpw = (n_tiles + grid - 1) / grid;
     }
-    hipLaunchKernelGGL(kern, dim3((unsigned)grid), dim3(256), lds, stream, b);
-    HMMR_CHECK_HIP(hipGetLastError());
-    return 0;
+    return launch_with_lds(kern, once, dim3((unsigned)grid), dim3(256), lds, lds, stream, b);
 }
 
 }  // namespace
@@ -1300,7 +1250,7 @@ int hmmr_unit_pair_split(const hmmr_tail_desc_t* d, hipStream_t stream) {
     a.probe = 0;
 #ifdef HMMR_GEMM_PROBE
     a.probe = hmmr_debug_state()->gemm_probe;
-    a.ts = (unsigned long long*)(((unsigned long long)(unsigned)hmmr_debug_state()->reserved[1] << 32) | (unsigned)hmmr_debug_state()->reserved[0]);
+    a.ts = probe_stamp_buffer();
 #endif
     // round 6: the wave-specialised form (two waves per SIMD) for the shapes with a shortcut tensor is built, bit-identical and measured
     // EQUAL to the one-wave-per-SIMD form (profiles/r06_pair_ws_*: 0.252 against 0.260 ms in block 3, 0.334 against 0.333 in block 2,
