@@ -81,6 +81,16 @@ class StemCounts(C.Structure):
     _fields_ = [(k, C.c_ulonglong) for k in ("fused", "fused_conv1", "repack", "gemm", "pool")]
 
 
+TILE_GENERIC, TILE_PATCH, TILE_STREAM_3X3, TILE_STREAM_1X1 = range(4)
+CONV_TILE_MAX = 63       # HMMR_CONV_TILE_MAX: tile numbers are 1 .. this
+
+
+class ConvTileInfo(C.Structure):
+    """hmmr_conv_tile_info_t: one row of the tile list (csrc/conv_tiles.h)."""
+    _fields_ = [(k, C.c_int) for k in ("tile", "family", "fm", "fn", "wgm", "wgn", "pixels", "channels", "row_blocks", "depth", "occupancy", "wmax",
+                                       "split_only", "conv3_form", "cols", "tune_cols", "narrow", "rank", "candidate")] + [("text", C.c_char_p)]
+
+
 class Layer(C.Structure):
     _fields_ = [("w", _vp), ("scale", _fp), ("shift", _fp), ("tile", C.c_int), ("k_order", C.c_int)]
 
@@ -255,6 +265,10 @@ SIGNATURES = {
     "hmmr_launch_counts": (None, [C.POINTER(LaunchCounts), C.c_int]),
     "hmmr_stem_launch_counts": (None, [C.POINTER(StemCounts), C.c_int]),
     "hmmr_conv_gemm": (C.c_int, [C.POINTER(ConvDesc), _vp]),
+    "hmmr_conv_tile_info": (C.c_int, [C.c_int, C.POINTER(ConvTileInfo)]),
+    "hmmr_conv_tile_for": (C.c_int, [C.c_int] * 6),
+    "hmmr_conv_tile_fits": (C.c_int, [C.c_int] * 8),
+    "hmmr_conv_tile_f_movie": (C.c_int, []),
     "hmmr_conv_splitk_workspace_bytes": (C.c_size_t, [C.c_int, C.c_int, C.c_int]),
     "hmmr_resnet50_workspace_bytes": (C.c_size_t, [C.c_int, C.c_int]),
     "hmmr_resnet50_fwd": (C.c_int, [C.POINTER(ResnetWeights), _fp, C.c_int, C.c_int, _fp, _vp, C.c_size_t, _vp,
@@ -369,6 +383,16 @@ def launch_counts(clear=False):
     c = LaunchCounts()
     load().hmmr_launch_counts(C.byref(c), int(bool(clear)))
     return {k: int(getattr(c, k)) for k, _ in LaunchCounts._fields_}
+
+
+def conv_tiles(family=None):
+    """[ConvTileInfo] of every value hmmr_conv_desc_t.tile takes, or of one family's (TILE_*), by number (hmmr_conv_tile_info)."""
+    lib, rows = load(), []
+    for t in range(1, CONV_TILE_MAX + 1):
+        r = ConvTileInfo()
+        if lib.hmmr_conv_tile_info(t, C.byref(r)) == 0 and family in (None, r.family):
+            rows.append(r)
+    return rows
 
 
 def stem_launch_counts(clear=False):

@@ -43,8 +43,8 @@ def _newer(src, dst):
 
 
 def _deps():
-    # every header of csrc/: a new one cannot be forgotten
-    return sorted(os.path.join(CSRC, h) for h in os.listdir(CSRC) if h.endswith(".h")) + [os.path.join(INCLUDE, "hmmr_hip.h")]
+    # every header of csrc/ and of include/: a new one cannot be forgotten
+    return sorted(os.path.join(d, h) for d in (CSRC, INCLUDE) for h in os.listdir(d) if h.endswith(".h"))
 
 
 def build(force=False, verbose=True):

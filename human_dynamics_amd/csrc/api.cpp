@@ -6,6 +6,7 @@
 
 #include <hip/hip_runtime.h>
 
+#include "conv_tiles.h"
 #include "hmmr_hip.h"
 
 static thread_local char g_err[512] = "";
@@ -58,6 +59,25 @@ int hmmr_cu_count(hipStream_t stream) {
 }
 
 extern "C" int hmmr_abi_version(void) { return HMMR_ABI_VERSION; }
+
+// ---- the conv tile list (csrc/conv_tiles.h), as the Python side, the tests and the tools read it
+extern "C" int hmmr_conv_tile_info(int tile, hmmr_conv_tile_info_t* out) {
+    const hmmr_conv_tile_info_t* r = conv_tiles::row(tile);
+    if (!r) { hmmr_set_error("hmmr_conv_tile_info: %d is no tile", tile); return -1; }
+    if (!out) { hmmr_set_error("hmmr_conv_tile_info: null argument"); return -1; }
+    *out = *r;
+    return 0;
+}
+extern "C" int hmmr_conv_tile_for(int k_order, int filter_1x1, int conv3_form, int cout, int dtype, int candidate) {
+    return conv_tiles::tile_for(k_order, filter_1x1, conv3_form, cout, dtype, candidate);
+}
+extern "C" int hmmr_conv_tile_fits(int tile, int k_order, int filter_1x1, int conv3_form, int cout, int dtype, int win, int ksteps) {
+    char why[256];
+    if (conv_tiles::fit(tile, conv_tiles::Problem{k_order, filter_1x1, conv3_form, cout, dtype, win, ksteps}, why, sizeof why) == 0) return 0;
+    hmmr_set_error("hmmr_conv_tile_fits: %s", why);
+    return -1;
+}
+extern "C" int hmmr_conv_tile_f_movie(void) { return HMMR_TILE_F_MOVIE; }
 extern "C" const char* hmmr_last_error(void) { return g_err; }
 
 // ---- run flags: every translation unit that splits values keeps a sticky device word (csrc/common.h) and registers its reader here

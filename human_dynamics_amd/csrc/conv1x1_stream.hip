@@ -25,6 +25,7 @@
 // other's loop -- for short K loops and the conv3 form's HBM-heavy epilogue.  DESIGN.md section 4.1.3 has the measurements.
 // Products and their order per output element: (w.hi x.lo, w.lo x.hi, w.hi x.hi) per 16-channel K step, steps in channel order -- the
 // same for every tile of this kernel (they differ from gemm_conv.hip's 32-channel steps by fp32 rounding of the accumulation only).
+#include "conv_tiles.h"
 #include "stream_kit.h"
 
 namespace {
@@ -448,7 +449,6 @@ int launch_s1(const S1Args& base, hipStream_t stream) {
     S1Args a = base;
     constexpr int BM = 32 * WGM * FM, NPX = (BM + 63) / 64;
     constexpr int lds = D * 8192 + D * NPX * 4096 + 2048;
-    HMMR_REQUIRE(a.nk >= D, "hmmr_conv_gemm: k_order 2 (1x1): cin must be at least %d channels for this tile", 16 * D);
     a.n_tiles = ((a.M + BM - 1) / BM) * a.tiles_n;
     auto kern = conv1x1_stream_kernel<FM, FN, WGM, WGN, D, EPI, IN2, RES, OUT2, OCC>;
     static DeviceOnce once;
@@ -461,6 +461,13 @@ int launch_s1_c3(const S1Args& a, hipStream_t stream) {
     if (a.in2) return a.out2 ? launch_s1<FM, FN, WGM, WGN, D, 1, true, false, true, OCC>(a, stream) : launch_s1<FM, FN, WGM, WGN, D, 1, true, false, false, OCC>(a, stream);
     if (a.res) return a.out2 ? launch_s1<FM, FN, WGM, WGN, D, 1, false, true, true, OCC>(a, stream) : launch_s1<FM, FN, WGM, WGN, D, 1, false, true, false, OCC>(a, stream);
     return a.out2 ? launch_s1<FM, FN, WGM, WGN, D, 1, false, false, true, OCC>(a, stream) : launch_s1<FM, FN, WGM, WGN, D, 0, false, false, false, OCC>(a, stream);
+}
+
+// ... of a tile shape that has one (conv_tiles::fit has refused the others)
+template <bool C3, int FM, int FN, int WGM, int WGN, int D, int OCC>
+int launch_s1_c3_if(const S1Args& a, hipStream_t stream) {
+    if constexpr (C3) return launch_s1_c3<FM, FN, WGM, WGN, D, OCC>(a, stream);
+    else { hmmr_set_error("hmmr_conv_gemm: k_order 2 (1x1): this tile shape has no conv3 form"); return -1; }
 }
 
 }  // namespace
@@ -487,7 +494,6 @@ int hmmr_conv1x1_stream(const hmmr_conv_desc_t* d, hipStream_t stream) {
     HMMR_REQUIRE(!d->out_b || (d->n_split % 128 == 0 && d->n_split > 0 && d->n_split < d->cout), "hmmr_conv_gemm: k_order 2 (1x1): n_split must be a multiple of 128 inside (0, cout)");
     HMMR_REQUIRE(M < (1ll << 31), "hmmr_conv_gemm: k_order 2 (1x1): more than 2^31 pixels");
     if (M <= 0) return 0;
-    hmmr_count_launch(HMMR_COUNT_CONV1X1_STREAM);
     S1Args a = {};
     a.in = (const char*)d->in; a.wstream = (const char*)d->w; a.scale = d->scale; a.shift = d->shift;
     a.out = d->out; a.ldo = d->ldo; a.relu = d->relu;
@@ -499,39 +505,23 @@ int hmmr_conv1x1_stream(const hmmr_conv_desc_t* d, hipStream_t stream) {
     a.nk = a.nk1 + a.C2 / 16;
     a.res = (const char*)d->res; a.out2 = d->out2; a.scale2 = d->scale2; a.shift2 = d->shift2;
     a.nt_stride = (long long)a.nk * 8192;
-    int tile = d->tile;
-    if (!tile) {
-        // the library's choice: fewest rounds of 256 workgroups x (row blocks per tile + ~1.5 for a tile's prologue and epilogue); the 7 x 1 / 8 x 1
-        // wave tiles read 16-18 fragments per 21-24 MFMAs and pay ~15 % for it (profiles/r05r: LDS bandwidth)
-        // (29, round 6: a 128-pixel tile for SHORT launches -- block 4's conv1 at 64 frames is 98 row blocks x 4 channel tiles: 52 workgroups of tile 25)
-        static const int cand[6][3] = {{25, 8, 6}, {24, 14, 4}, {26, 8, 3}, {22, 7, 6}, {23, 8, 6}, {29, 4, 6}};      // tile, row blocks, ring depth
-        const long long rbs = (M + 31) / 32;
-        double best = 0;
-        for (const auto& cd : cand) {
-            if (a.nk < cd[2] || (c3 && cd[0] != 24 && cd[0] != 25 && cd[0] != 26)) continue;      // (the conv3 form's epilogue tiles live in the idle rings: a 128-pixel tile's are too small)
-            const long long tiles = ((rbs + cd[1] - 1) / cd[1]) * a.tiles_n;
-            double cost = (double)((tiles + 255) / 256) * (cd[1] + 1.5) * (cd[0] == 22 || cd[0] == 23 ? 1.15 : 1.0);
-            // tile 26 (two workgroups per CU): a round is 512 workgroups and takes two tiles' time, less what one workgroup's prologue,
-            // epilogue and round trips hide under the other's loop -- measured (profiles/r05v): 0.8 of it for the conv3 form (its epilogue is
-            // HBM time), 0.88 for a short K loop, nothing gained on a long one
-            if (cd[0] == 26) cost = (double)((tiles + 511) / 512) * 2.0 * (cd[1] + 1.5) * (c3 ? 0.8 : a.nk <= 32 ? 0.88 : 1.05);
-            if (!tile || cost < best) { tile = cd[0]; best = cost; }
-        }
-    }
-    HMMR_REQUIRE(tile, "hmmr_conv_gemm: k_order 2 (1x1): cin must be at least 64 channels (the rings are 4 K steps deep)");
-    if (c3) {
-        HMMR_REQUIRE(tile >= 24 && tile <= 26, "hmmr_conv_gemm: k_order 2 (1x1): the conv3 form (res / out2 / in2) runs tiles 24 .. 26, not %d", tile);
-        return tile == 24 ? launch_s1_c3<7, 2, 2, 2, 4>(a, stream) : tile == 25 ? launch_s1_c3<4, 2, 2, 2, 6>(a, stream) : launch_s1_c3<4, 2, 2, 2, 3, 2>(a, stream);
+    // tile = 0: the library's choice (conv_tiles::choose_s1)
+    const int tile = d->tile ? d->tile : conv_tiles::choose_s1(M, d->cout, a.nk, c3);
+    HMMR_REQUIRE(tile, "hmmr_conv_gemm: k_order 2 (1x1): cin must be at least %d channels (the shallowest rings are %d K steps deep)",
+                 16 * conv_tiles::s1_min_depth(), conv_tiles::s1_min_depth());
+    char why[256];
+    HMMR_REQUIRE(!conv_tiles::fit(tile, conv_tiles::Problem{2, 1, c3, d->cout, d->in_dtype, 0, a.nk}, why, sizeof why), "hmmr_conv_gemm: %s", why);
+    hmmr_count_launch(HMMR_COUNT_CONV1X1_STREAM);
+    if (c3) switch (tile) {      // the conv3 forms first, then the plain epilogues: the order the kernels have always been instantiated in
+#define X(ID, FM, FN, WGM, WGN, D, OCC, C3, ...) case ID: return launch_s1_c3_if<C3, FM, FN, WGM, WGN, D, OCC>(a, stream);
+        HMMR_S1_TILES(X)
+#undef X
+        default: hmmr_set_error("hmmr_conv_gemm: k_order 2 (1x1): no tile %d", tile); return -1;
     }
     switch (tile) {
-    case 22: return launch_s1<7, 1, 1, 4, 6>(a, stream);       // 224 pixels, every wave all of them and 32 of the 128 channels
-    case 23: return launch_s1<8, 1, 1, 4, 6>(a, stream);       // 256 pixels, likewise
-    case 24: return launch_s1<7, 2, 2, 2, 4>(a, stream);       // 448 pixels, waves 2 x 2
-    case 25: return launch_s1<4, 2, 2, 2, 6>(a, stream);       // 256 pixels, waves 2 x 2
-    case 26: return launch_s1<4, 2, 2, 2, 3, 0, false, false, false, 2>(a, stream);       // 256 pixels, TWO workgroups per CU (rings 3 deep)
-    case 29: return launch_s1<2, 2, 2, 2, 6>(a, stream);       // 128 pixels, waves 2 x 2: short launches
-    default: break;
+#define X(ID, FM, FN, WGM, WGN, D, OCC, ...) case ID: return launch_s1<FM, FN, WGM, WGN, D, 0, false, false, false, OCC>(a, stream);
+        HMMR_S1_TILES(X)
+#undef X
+        default: hmmr_set_error("hmmr_conv_gemm: k_order 2 (1x1): no tile %d", tile); return -1;
     }
-    hmmr_set_error("hmmr_conv_gemm: k_order 2 (1x1) runs tiles 22 .. 26 and 29, not %d", tile);
-    return -1;
 }

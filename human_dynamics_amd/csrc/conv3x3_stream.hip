@@ -29,6 +29,7 @@
 // Products and their order per output element: (w.hi x.lo, w.lo x.hi, w.hi x.hi) per K step, K steps in stream order -- the
 // same for every tile shape, so every tile of this kernel produces the same bits (they differ from k_order 0 / 1 by the fp32
 // rounding of a different summation order only).
+#include "conv_tiles.h"
 #include "stream_kit.h"
 
 namespace {
@@ -389,9 +390,10 @@ int launch_s3_t(const S3Args& base, int cout, hipStream_t stream) {
     return launch_with_lds(kern, once, dim3((unsigned)a.n_tiles), dim3(256), lds, lds, stream, a);
 }
 
-template <int FM, int FN, int WGM, int WGN, int WMAX>
+template <int FM, int FN, int WGM, int WGN, int WMAX, bool SPLIT_ONLY>
 int launch_s3(const S3Args& a, int cout, bool split, hipStream_t stream) {
-    return split ? launch_s3_t<FM, FN, WGM, WGN, WMAX, true>(a, cout, stream) : launch_s3_t<FM, FN, WGM, WGN, WMAX, false>(a, cout, stream);
+    if constexpr (SPLIT_ONLY) return launch_s3_t<FM, FN, WGM, WGN, WMAX, true>(a, cout, stream);      // (conv_tiles::fit has refused bf16 operands)
+    else return split ? launch_s3_t<FM, FN, WGM, WGN, WMAX, true>(a, cout, stream) : launch_s3_t<FM, FN, WGM, WGN, WMAX, false>(a, cout, stream);
 }
 
 }  // namespace
@@ -409,7 +411,6 @@ int hmmr_conv3x3_stream(const hmmr_conv_desc_t* d, hipStream_t stream) {
     HMMR_REQUIRE(split || d->cin % 64 == 0, "hmmr_conv_gemm: k_order 2 with bf16 tensors needs cin %% 64 == 0 (K steps of 32 channels, taken in pairs)");
     HMMR_REQUIRE(d->cin % 32 == 0 && (d->cout % 128 == 0 || d->cout == 64) && d->win <= 56 && d->scale && d->shift,
                  "hmmr_conv_gemm: k_order 2 needs cin %% 32 == 0, cout %% 128 == 0 (or cout = 64), an image at most 56 pixels wide and scale + shift");
-    hmmr_count_launch(HMMR_COUNT_CONV3X3_STREAM);
     S3Args a = {};
     a.in = (const char*)d->in; a.wstream = (const char*)d->w; a.scale = d->scale; a.shift = d->shift;
     a.out = d->out; a.ldo = d->ldo;
@@ -418,45 +419,15 @@ int hmmr_conv3x3_stream(const hmmr_conv_desc_t* d, hipStream_t stream) {
 #ifdef HMMR_GEMM_PROBE
     a.ts = probe_stamp_buffer();
 #endif
-    int tile = d->tile;
-    const bool narrow = d->cout == 64, wide = d->win > 28;
-    if (!tile) {
-        // the library's choice: fewest rounds of 256 workgroups x (row blocks per tile + ~1.5 for a tile's prologue and epilogue)
-        // (27 / 28, round 6: 128- and 192-pixel tiles for SHORT launches -- at the reference's own batch sizes, 64 frames of FeatureExtractor
-        //  and the 160 of Tester.predict, blocks 3-4 are 98 - 245 row blocks: 56 - 140 workgroups of the 224-pixel tile on 256 CUs)
-        static const int cand[9][3] = {{12, 14, 0}, {13, 8, 0}, {15, 12, 0}, {16, 10, 0}, {21, 7, 0}, {27, 4, 0}, {28, 6, 0}, {19, 20, 1}, {20, 16, 1}};
-        const long long rbs = (a.M + 31) / 32, nts = narrow ? 1 : d->cout / 128;
-        double best = 0;
-        for (const auto& cd : cand) {
-            if ((cd[2] != 0) != narrow || ((cd[0] == 21 || cd[0] == 27 || cd[0] == 28) && !split)) continue;
-            const long long tiles = ((rbs + cd[1] - 1) / cd[1]) * nts;
-            const double cost = (double)((tiles + 255) / 256) * (cd[1] + 1.5);
-            if (!tile || cost < best) { tile = cd[0]; best = cost; }
-        }
-    }
-    HMMR_REQUIRE((tile == 19 || tile == 20) == narrow && (!wide || narrow), "hmmr_conv_gemm: k_order 2: tiles 12 .. 18, 21, 27, 28 take cout %% 128 == 0 and images up to 28 pixels wide, "
-                 "tiles 19 / 20 cout = 64 and up to 56 (tile %d, cout %d, win %d)", tile, d->cout, d->win);
+    // tile = 0: the library's choice (conv_tiles::choose_s3); every tile is asked whether it takes the columns, the operands and the image
+    const int tile = d->tile ? d->tile : conv_tiles::choose_s3(a.M, d->cout, split);
+    char why[256];
+    HMMR_REQUIRE(!conv_tiles::fit(tile, conv_tiles::Problem{2, 0, 0, d->cout, d->in_dtype, d->win, 0}, why, sizeof why), "hmmr_conv_gemm: %s", why);
+    hmmr_count_launch(HMMR_COUNT_CONV3X3_STREAM);
     switch (tile) {
-    case 12: return launch_s3<7, 2, 2, 2, 28>(a, d->cout, split, stream);       // 448 pixels
-    case 13: return launch_s3<4, 2, 2, 2, 28>(a, d->cout, split, stream);       // 256
-    case 14: return launch_s3<8, 2, 2, 2, 28>(a, d->cout, split, stream);       // 512
-    case 15: return launch_s3<6, 2, 2, 2, 28>(a, d->cout, split, stream);       // 384
-    case 16: return launch_s3<5, 2, 2, 2, 28>(a, d->cout, split, stream);       // 320
-    case 17: return launch_s3<4, 4, 4, 1, 28>(a, d->cout, split, stream);       // 512, waves split the pixels
-    case 18: return launch_s3<3, 4, 4, 1, 28>(a, d->cout, split, stream);       // 384
-    case 19: return launch_s3<5, 2, 4, 1, 56>(a, d->cout, split, stream);       // 640 pixels x 64 channels
-    case 20: return launch_s3<4, 2, 4, 1, 56>(a, d->cout, split, stream);       // 512 x 64
-    case 21:                                                                    // 224 pixels, every wave all of them and 32 of the 128 channels
-        HMMR_REQUIRE(split, "hmmr_conv_gemm: k_order 2, tile 21 (7 x 1 accumulators per wave) is built for split tensors: with two MFMAs per step "
-                     "the bf16 form has no room for its 16 fragment reads");
-        return launch_s3_t<7, 1, 1, 4, 28, true>(a, d->cout, stream);
-    case 27:                                                                    // 128 pixels x 128 channels (2 x 2 accumulators per wave): short launches
-    case 28:                                                                    // 192 pixels (3 x 2)
-        HMMR_REQUIRE(split, "hmmr_conv_gemm: k_order 2, tiles 27 / 28 (2 x 2 and 3 x 2 accumulators per wave) are built for split tensors: with two MFMAs "
-                     "per step the bf16 form has no room for their fragment reads");
-        return tile == 27 ? launch_s3_t<2, 2, 2, 2, 28, true>(a, d->cout, stream) : launch_s3_t<3, 2, 2, 2, 28, true>(a, d->cout, stream);
-    default: break;
+#define X(ID, FM, FN, WGM, WGN, WMAX, SPLIT_ONLY, ...) case ID: return launch_s3<FM, FN, WGM, WGN, WMAX, SPLIT_ONLY>(a, d->cout, split, stream);
+        HMMR_S3_TILES(X)
+#undef X
+        default: hmmr_set_error("hmmr_conv_gemm: k_order 2: no tile %d", tile); return -1;
     }
-    hmmr_set_error("hmmr_conv_gemm: k_order 2 runs tiles 12 .. 21, 27 and 28, not %d", tile);
-    return -1;
 }

@@ -36,6 +36,7 @@
 #include <string.h>
 #include <type_traits>
 
+#include "conv_tiles.h"
 #include "stream_kit.h"
 
 struct ConvArgs {
@@ -1032,28 +1033,36 @@ static int launch_patch(const ConvArgs& base, hipStream_t stream) {
     return launch_with_lds(kern, once, dim3(a.n_tiles), dim3(512), 160 * 1024, lds, stream, a);
 }
 
-template <typename TA, typename TO>
-static int launch_patch_tiled(const ConvArgs& a, int tile, hipStream_t stream) {
-    const int bm = tile == 10 ? 128 : 256;
-    const int npp = (patch_rows_bound(bm, a.Hin, a.Win) + 63) / 64;
-    if (tile == 9) {
-        if (npp <= 5) return launch_patch<TA, TO, 256, 128, 4, 2, 5>(a, stream);
-        if (npp <= 7) return launch_patch<TA, TO, 256, 128, 4, 2, 7>(a, stream);
-    } else if (tile == 10) {
-        if (npp <= 3) return launch_patch<TA, TO, 128, 256, 2, 4, 3>(a, stream);
-        if (npp <= 4) return launch_patch<TA, TO, 128, 256, 2, 4, 4>(a, stream);
-    } else if (tile == 11) {
+// one patch tile at the patch depth NPP its image needs: two depths per shape, the smaller for the ResNet's narrow images, the larger what LDS holds
+template <typename TA, typename TO, int BM, int BN, int WGM, int WGN, bool PIPE>
+static int launch_patch_npp(const ConvArgs& a, int tile, hipStream_t stream) {
+    const int npp = (patch_rows_bound(BM, a.Hin, a.Win) + 63) / 64;
+    if constexpr (PIPE) {
         if constexpr (std::is_same<TA, bsplit_t>::value) {
             if (npp <= 5) return launch_pipe<TA, TO, 5>(a, stream);
             if (npp <= 6) return launch_pipe<TA, TO, 6>(a, stream);
         }
+    } else if constexpr (BM == 256) {
+        if (npp <= 5) return launch_patch<TA, TO, BM, BN, WGM, WGN, 5>(a, stream);
+        if (npp <= 7) return launch_patch<TA, TO, BM, BN, WGM, WGN, 7>(a, stream);
     } else {
-        hmmr_set_error("hmmr_conv_gemm: k_order 1 runs tiles 9 / 11 (256x128) and 10 (128x256), not %d", tile);
-        return -1;
+        if (npp <= 3) return launch_patch<TA, TO, BM, BN, WGM, WGN, 3>(a, stream);
+        if (npp <= 4) return launch_patch<TA, TO, BM, BN, WGM, WGN, 4>(a, stream);
     }
     hmmr_set_error("hmmr_conv_gemm: k_order 1, tile %d: a %d x %d image needs a patch of %d x 64 rows, more than LDS holds",
                    tile, a.Hin, a.Win, npp);
     return -1;
+}
+
+// (the caller has asked conv_tiles::fit)
+template <typename TA, typename TO>
+static int launch_patch_tiled(const ConvArgs& a, int tile, hipStream_t stream) {
+    switch (tile) {
+#define X(ID, BM, BN, WGM, WGN, PIPE, ...) case ID: return launch_patch_npp<TA, TO, BM, BN, WGM, WGN, PIPE>(a, tile, stream);
+        HMMR_PATCH_TILES(X)
+#undef X
+        default: hmmr_set_error("hmmr_conv_gemm: k_order 1: no tile %d", tile); return -1;
+    }
 }
 
 // ------------------------------------------------------------------------- //
@@ -1079,32 +1088,19 @@ static int launch_cfg(const ConvArgs& base, int slices, hipStream_t stream) {
 
 template <typename TA, typename TO, bool PRO, bool UTAP>
 static int launch_tiled(const ConvArgs& a, int tile, int slices, hipStream_t stream) {
-    switch (tile) {   // BM, BN, waves along M, waves along N
-        case 1: return launch_cfg<TA, TO, 128, 128, 2, 2, PRO, UTAP, 2>(a, slices, stream);   // 4 waves, 64x64 each
-        case 2: return launch_cfg<TA, TO, 128, 64, 2, 2, PRO, UTAP, 2>(a, slices, stream);    // 4 waves, 64x32 each
-        case 3: return launch_cfg<TA, TO, 64, 64, 2, 2, PRO, UTAP, 2>(a, slices, stream);     // 4 waves, 32x32 each
-        case 5: return launch_cfg<TA, TO, 128, 128, 4, 2, PRO, UTAP, 2>(a, slices, stream);   // 8 waves, 32x64 each
-        case 6: return launch_cfg<TA, TO, 128, 64, 4, 2, PRO, UTAP, 2>(a, slices, stream);    // 8 waves, 32x32 each
-        // deep ring + ping-pong wave groups, one 8-wave workgroup per CU (256 VGPRs per lane).  128x128 and 256x64 variants
-        // of this structure were measured 15-40 % slower than tiles 5 / 6 on every ResNet shape and are not instantiated; 128x256 (tile 8) is the faster 3x3 tile.
-        case 7: return launch_cfg<TA, TO, 256, 128, 4, 2, PRO, UTAP, 3>(a, slices, stream);   // 64x64 each, 3 x 48 KB
-        case 8: return launch_cfg<TA, TO, 128, 256, 2, 4, PRO, UTAP, 3>(a, slices, stream);   // 64x64 each; half the A rows: half the fused-preact work per MFMA
-        default: hmmr_set_error("hmmr_conv_gemm: bad tile %d", tile); return -1;
+    switch (tile) {
+#define X(ID, BM, BN, WGM, WGN, NSTAGE, ...) case ID: return launch_cfg<TA, TO, BM, BN, WGM, WGN, PRO, UTAP, NSTAGE>(a, slices, stream);
+        HMMR_GENERIC_TILES(X)
+#undef X
+        default: hmmr_set_error("hmmr_conv_gemm: k_order 0: no tile %d", tile); return -1;
     }
 }
 
 template <typename TA, typename TO>
 static int launch_typed(const ConvArgs& a, int tile, int slices, hipStream_t stream) {
-    if (tile == 0) {
-        // Measured on the ResNet-50 shapes at batch 256 (tools/conv_bench.py): 8-wave workgroups
-        // (4 waves per SIMD at 2 workgroups per CU) beat 4-wave ones by 5-20 %, and a tile count of
-        // ~1.5x the CU count with 128x128 tiles beats twice as many 128x64 tiles.
-        const long long t128 = (long long)((a.M + 127) / 128) * ((a.cout + 127) / 128);
-        const long long t12864 = (long long)((a.M + 127) / 128) * ((a.cout + 63) / 64);
-        if (a.cout >= 128 && a.cout % 128 == 0 && t128 * slices >= 192) tile = 5;
-        else if (t12864 * slices >= 192) tile = 6;
-        else tile = 3;
-    }
+    if (tile == 0) tile = conv_tiles::choose_generic(a.M, a.cout, slices);
+    char why[256];
+    HMMR_REQUIRE(!conv_tiles::fit(tile, conv_tiles::Problem{0, 0, 0, a.cout, -1, 0, 0}, why, sizeof why), "hmmr_conv_gemm: %s", why);
     const bool utap = ((size_t)1 << a.cin_log2) * sizeof(TA) >= 128;
     if (a.pro_scale) {
         if (!utap) { hmmr_set_error("hmmr_conv_gemm: fused pre-activation needs cin*sizeof >= 128"); return -1; }
@@ -1231,7 +1227,9 @@ extern "C" int hmmr_conv_gemm(const hmmr_conv_desc_t* d, void* stream) {
     HMMR_REQUIRE(!d->pro_scale || !d->res, "hmmr_conv_gemm: a fused pre-activation (pro_*) cannot be combined with a residual");
     HMMR_REQUIRE(!d->pro_scale || (d->py == 0 && d->px == 0 && d->kh == 1 && d->kw == 1),
                  "hmmr_conv_gemm: the fused pre-activation is for un-padded 1x1 gathers (padding must stay zero)");
-    HMMR_REQUIRE(d->tile != 8 || d->cout % 256 == 0, "hmmr_conv_gemm: tile 8 (128x256) needs cout %% 256 == 0 (filter rows are padded to 128)");
+    char why[256];
+    if (const hmmr_conv_tile_info_t* t = conv_tiles::row(d->tile); t && t->family == HMMR_TILE_GENERIC)      // (a generic tile's columns: also for an empty problem and before k_order is read)
+        HMMR_REQUIRE(!conv_tiles::fit(d->tile, conv_tiles::Problem{0, 0, 0, d->cout, -1, 0, 0}, why, sizeof why), "hmmr_conv_gemm: %s", why);
     HMMR_REQUIRE(!d->in2 || (d->kh == 1 && d->kw == 1 && d->py == 0 && d->px == 0 && d->sy == 1 && d->sx == 1 && !d->pro_scale &&
                              d->split_k <= 1 && d->cin2 > 0 && d->cin % bke == 0 && d->cin2 % bke == 0 &&
                              d->in_px_stride == d->cin && d->in_row_stride == d->win * d->cin &&
@@ -1275,14 +1273,9 @@ extern "C" int hmmr_conv_gemm(const hmmr_conv_desc_t* d, void* stream) {
         if (d->k_order == 2) return hmmr_conv3x3_stream(d, s);
         const bool px3 = d->in_dtype == HMMR_F16X3 && d->out_dtype == HMMR_F16X3, pbf = d->in_dtype == HMMR_BF16 && d->out_dtype == HMMR_BF16;
         HMMR_REQUIRE(px3 || pbf, "hmmr_conv_gemm: k_order 1 is built for split (f16x3) and bf16 tensors");
-        // library's choice: the 256x128 ping-pong tile (inside the network the tuner prefers it to tile 11 on ten layers of eleven,
-        // profiles/r03p; tile 10 needs 256 output columns and a narrower image)
-        const int ptile = d->tile ? d->tile : 9;
-        HMMR_REQUIRE((ptile == 10 ? d->cout % 256 : d->cout % 128) == 0, "hmmr_conv_gemm: k_order 1: cout must fill the tile's columns (filter rows are padded to 128)");
-        if (pbf) {
-            HMMR_REQUIRE(ptile != 11, "hmmr_conv_gemm: k_order 1, tile 11 (no load segment) is written for split operands; bf16 runs tiles 9 / 10");
-            return launch_patch_tiled<bf16_t, bf16_t>(a, ptile, s);
-        }
+        const int ptile = d->tile ? d->tile : conv_tiles::choose_patch();
+        HMMR_REQUIRE(!conv_tiles::fit(ptile, conv_tiles::Problem{1, 0, 0, d->cout, d->in_dtype, 0, 0}, why, sizeof why), "hmmr_conv_gemm: %s", why);
+        if (pbf) return launch_patch_tiled<bf16_t, bf16_t>(a, ptile, s);
         return launch_patch_tiled<bsplit_t, bsplit_t>(a, ptile, s);
     }
     const bool in16 = d->in_dtype == HMMR_BF16, in32 = d->in_dtype == HMMR_F32, inx3 = d->in_dtype == HMMR_F16X3;

@@ -17,6 +17,7 @@
 #include <string>
 #include <vector>
 
+#include "conv_tiles.h"
 #include "hmmr_hip.h"
 
 void hmmr_set_error(const char* fmt, ...);
@@ -558,7 +559,7 @@ void pack_temporal(const Vars& v, int dtype, int num_blocks, Blob& b, hmmr_tempo
         t.conv1 = layer(b, rows, R, K, dtype, nullptr, 0, v.get(c1 + "/biases", 2048), 2048);
         conv_rows(v.get(c2 + "/weights", (int64_t)3 * 2048 * 2048), 3, 2048, 2048, 0, 32, rows, R, K);
         t.conv2 = layer(b, rows, R, K, dtype, nullptr, 0, v.get(c2 + "/biases", 2048), 2048);
-        if (dtype == HMMR_F16X3) t.conv1.tile = t.conv2.tile = 8;   // the 128x256 ping-pong tile with 5 K slices (csrc/temporal.hip)
+        if (dtype == HMMR_F16X3) t.conv1.tile = t.conv2.tile = HMMR_TILE_F_MOVIE;
     }
 }
 

@@ -248,29 +248,10 @@ class HmmrEngine(object):
 
     @staticmethod
     def _tile_for(lay, cand, cout, dtype=None, nm="conv2"):
-        """hmmr_layer_t.tile for candidate `cand` on a layer with `cout` output columns: 0 (the library's choice) where
-        the tile does not fit; a layer packed chunk-major (k_order 1, the 3x3 patch kernels) runs tiles 9 / 10, the patch
-        forms of 7 / 8, or 11, the 256x128 tile without a load segment; a k_order 2 layer (csrc/conv3x3_stream.hip) takes the
-        tuner's candidates as its own tile shapes 13 .. 18; a k_order 2 layer with a 1x1 filter (any layer name but conv2; csrc/conv1x1_stream.hip)
-        tiles 22 .. 26, its conv3 form 24 .. 26."""
-        if lay.k_order == 2 and nm != "conv2":
-            t = {5: 22, 6: 23, 3: 24, 1: 25, 2: 26, 4: 29}.get(cand, cand if (22 <= cand <= 26 or cand == 29) else 0)
-            return 0 if (nm == "conv3" and t in (22, 23, 29)) else t
-        if lay.k_order == 2:                                 # the stream kernel's tiles: 12 .. 18 and 21 (128-channel tiles), 19 / 20 (64 channels)
-            if cout == 64:
-                return {5: 19, 6: 20}.get(cand, cand if cand in (19, 20) else 0)
-            t = {5: 13, 6: 14, 3: 15, 1: 16, 2: 17, 7: 18, 8: 12, 11: 21, 4: 27, 9: 28}.get(cand, cand if (12 <= cand <= 18 or cand in (21, 27, 28)) else 0)
-            return 0 if (t in (21, 27, 28) and dtype == L.HMMR_BF16) else t       # (the 7 x 1, 2 x 2 and 3 x 2 wave tiles are built for split tensors)
-        if lay.k_order:
-            cand = {7: 9, 8: 10}.get(cand, cand)
-            if cand == 11 and dtype == L.HMMR_BF16:          # the tile without a load segment is written for split operands
-                return 0
-            return cand if (cand in (9, 11) and cout % 128 == 0) or (cand == 10 and cout % 256 == 0) else 0
-        # the generic kernel's tiles are 1, 2, 3, 5 .. 8: anything else (the tuner's candidate 4 is a stream-kernel shape only; a cached table written under another packing configuration, e.g. 22 .. 26
-        # of a 1x1 stream layer read back with STREAM_1X1 off) becomes the library's choice instead of a 'bad tile' error in the pass
-        if cand not in (1, 2, 3, 5, 6, 7, 8) or (cand in (1, 5, 7) and cout % 128) or (cand == 8 and cout % 256):
-            return 0
-        return cand
+        """hmmr_layer_t.tile for candidate `cand` (a tuner candidate or a tile number) on a layer with `cout` output columns, launched
+        under the name `nm`: 0 (the library's choice) where nothing of the layer's kernel family fits.  The rule and the candidate maps are
+        the tile list's (csrc/conv_tiles.h: hmmr_conv_tile_for)."""
+        return L.load().hmmr_conv_tile_for(lay.k_order, int(nm != "conv2"), int(nm == "conv3"), cout, -1 if dtype is None else dtype, cand)
 
     def _layer_cout(self, u, nm):
         U = self.rw.unit[u]

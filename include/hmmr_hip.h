@@ -146,19 +146,11 @@ typedef struct {
     int64_t res_img_stride;
     int res_row_stride, res_px_stride;
     int relu;              /* ReLU on `out` after the residual add */
-    int tile;              /* 0 = auto; 4-wave tiles: 1 = 128x128, 2 = 128x64, 3 = 64x64;
-                              8-wave tiles: 5 = 128x128, 6 = 128x64 (two workgroups per CU, 2 LDS stages);
-                              7 = 256x128, 8 = 128x256 (one workgroup per CU: 3-stage LDS ring, ping-pong wave groups);
-                              k_order 1 only: 9 = 256x128, 10 = 128x256 (the same structure, A operand out of an input patch),
-                              11 = 256x128 without a load segment (two fragment sets per wave, one barrier per K step);
-                              k_order 2 only (csrc/conv3x3_stream.hip; 4 waves, one per SIMD, 128 output channels per tile): 12 = 448 pixels
-                              (wave tile 7 x 2 accumulators of 32 x 32), 13 = 256 (4 x 2), 14 = 512 (8 x 2), 15 = 384 (6 x 2), 16 = 320 (5 x 2);
-                              17 = 512, 18 = 384 pixels with the waves splitting the pixels (4 x 4 / 3 x 4); 19 = 640, 20 = 512 pixels x 64 channels
-                              (cout = 64, images up to 56 pixels wide); 21 = 224 pixels, every wave all of them and 32 channels (7 x 1; split only);
-                              k_order 2 with a 1x1 filter only (csrc/conv1x1_stream.hip; 4 waves, one per SIMD, 128 output channels per tile, both
-                              operands through LDS rings): 22 = 224 pixels (7 x 1 accumulators per wave, every wave 32 of the channels),
-                              23 = 256 pixels (8 x 1), 24 = 448 pixels (7 x 2, waves 2 x 2), 25 = 256 pixels (4 x 2, waves 2 x 2),
-                              26 = 256 pixels (4 x 2) with TWO workgroups per CU (rings 3 deep, 256 registers per wave) */
+    int tile;              /* 0 = the library's choice; otherwise the number of one tile shape of the kernel family the descriptor selects: the
+                              generic implicit GEMM (k_order 0), the 3x3 patch kernels (k_order 1), the 3x3 stream kernel (k_order 2) or the 1x1
+                              stream kernel (k_order 2, kh = kw = 1).  csrc/conv_tiles.h lists every tile once -- shape, the columns and operands
+                              it takes, its place in the library's choice --, hmmr_conv_tile_info returns a row of that list.  A tile that does
+                              not fit the problem is refused (rc -1) before anything is queued; no tile changes a result bit inside its family. */
     /* split-K (for GEMMs with few output tiles and a long K): split_k > 1 slices K into that many
      * contiguous ranges, each range leaves an fp32 partial plane in `ws`, and a second launch adds the
      * planes IN SLICE ORDER and applies the epilogue.  The caller fixes split_k per layer (never from
@@ -190,7 +182,7 @@ typedef struct {
      * kernel: a workgroup keeps the 128-byte channel chunk of every input pixel its tile touches (a PATCH: the tile's
      * pixels and a halo of win + 1 pixels on either side) in LDS and reads the nine taps of that chunk as nine shifted
      * fragment sets (out-of-image taps read a zero row), so an input
-     * line leaves L2 once per chunk instead of once per tap (tiles 9 / 10 / 11; scale/shift/relu epilogue only: no res,
+     * line leaves L2 once per chunk instead of once per tap (the patch tiles; scale/shift/relu epilogue only: no res,
      * out2, out_b, pro_scale, in2, split_k).  The sum over k is the same set of products in another order: results
      * differ from k_order 0 by fp32 rounding of the accumulation only.
      * 2: `w` is not a matrix but the FILTER STREAM of packing.pack_conv3x3_stream (hmmr_conv3x3_stream_bytes(cin, cout) bytes):
@@ -198,12 +190,13 @@ typedef struct {
      * A-operand fragments (lane = 32 * (k half) + row; 8 halves = W[row][16 (ci / 16) + 8 half .. + 7] of that tap), rows scaled
      * like every split filter bank.  Same convolutions and epilogue as k_order 1; split (f16x3) tensors, cin % 32 == 0 -- or bf16 tensors (K steps of 32
      * channels `(ci / 32) * 9 + tap`, the two planes = the two 16-wide MFMA chunks, no row scaling), cin % 64 == 0 --,
-     * cout % 128 == 0 and win <= 28 (tiles 12 .. 18, 21) or cout = 64 and win <= 56 (tiles 19 / 20) (csrc/conv3x3_stream.hip).  Every tile produces the same bits.
-     * 2 with kh = kw = 1 (round 5; csrc/conv1x1_stream.hip, tiles 22 .. 26): `w` is the stream of packing.pack_conv1x1_stream
+     * cout % 128 == 0 or cout = 64, each with tiles of its own and its own widest image (csrc/conv3x3_stream.hip; the 3x3 stream rows of
+     * csrc/conv_tiles.h).  Every tile produces the same bits.
+     * 2 with kh = kw = 1 (round 5; csrc/conv1x1_stream.hip, the 1x1 stream rows): `w` is the stream of packing.pack_conv1x1_stream
      * (hmmr_conv1x1_stream_bytes(cin + cin2, cout) bytes: K steps of 16 input channels, the same 8 KB per 128 output channels as one tap above).  A
-     * stride-1 1x1 convolution over a dense [M][cin] split tensor, cin % 16 == 0 (at least 64: the rings are 4-6 K steps deep), cout % 128 == 0,
+     * stride-1 1x1 convolution over a dense [M][cin] split tensor, cin % 16 == 0 (at least as many K steps as the tile's rings are deep), cout % 128 == 0,
      * scale and shift given; no pro_scale, split_k, batch.  Two epilogues: scale / shift / relu with the out_b column split (n_split % 128 == 0), or
-     * -- with any of res / out2 / in2, tiles 24 .. 26 -- the conv3 form: in2 continues K (cin2 % 16 == 0; not together with res), res is a dense
+     * -- with any of res / out2 / in2, on the tiles that have one -- the conv3 form: in2 continues K (cin2 % 16 == 0; not together with res), res is a dense
      * shortcut tensor with ldr == ldo, out2 = relu(scale2 * stored(out) + shift2) exactly as k_order 0 defines it.
      * Both operands go through LDS rings (one wave per SIMD), for layers whose K loop is bound by the round trip of
      * a two-stage ring (block 4, block3/unit_1's shortcut + conv1).  Differs from k_order 0 by fp32 rounding of the accumulation only. */
@@ -216,6 +209,39 @@ typedef struct {
     int batch;
     int64_t batch_in_bytes, batch_w_bytes, batch_out_bytes, batch_res_bytes, batch_scale_bytes, batch_shift_bytes;
 } hmmr_conv_desc_t;
+
+/* One row of the tile list (csrc/conv_tiles.h): everything that is known about one value of hmmr_conv_desc_t.tile. */
+#define HMMR_CONV_TILE_MAX 63    /* tile numbers are 1 .. HMMR_CONV_TILE_MAX (csrc/conv_tiles.h refuses a row beyond it at compile time) */
+enum { HMMR_TILE_GENERIC = 0, HMMR_TILE_PATCH = 1, HMMR_TILE_STREAM_3X3 = 2, HMMR_TILE_STREAM_1X1 = 3 };
+typedef struct {
+    int tile, family;          /* HMMR_TILE_* */
+    int fm, fn, wgm, wgn;      /* the 32 x 32 accumulators of one wave (pixels x channels), and the waves along pixels x channels */
+    int pixels, channels;      /* of one tile: 32 wgm fm x 32 wgn fn */
+    int row_blocks;            /* pixels / 32 */
+    int depth;                 /* LDS stages of the K loop (the 1x1 stream kernel: ring depth = the fewest K steps it takes; 0: not staged that way) */
+    int occupancy;             /* workgroups per CU */
+    int wmax;                  /* widest image in pixels; 0 = no limit of the tile's own */
+    int split_only;            /* built for split (f16x3) operands only */
+    int conv3_form;            /* 1x1 stream: has the res / out2 / in2 epilogue */
+    int cols;                  /* cout it takes: 0 = any, 64 = exactly 64, otherwise cout % cols == 0 */
+    int tune_cols;             /* hmmr_conv_tile_for offers it only when cout % tune_cols == 0 (0 = any) */
+    int narrow;                /* a 64-column tile (cols == 64) */
+    int rank;                  /* place among the library's candidates for tile = 0 (1 first); 0 = never chosen */
+    int candidate;             /* the tuner candidate that maps onto it; 0 = none */
+    const char* text;          /* short description, static storage */
+} hmmr_conv_tile_info_t;
+/* the row of `tile`; rc -1 for a number that is no tile (0 and the tuner's candidates that are no tile among them) */
+int hmmr_conv_tile_info(int tile, hmmr_conv_tile_info_t* out);
+/* the tile a layer runs for a tuner candidate or a literal tile number: k_order as packed, filter_1x1 / conv3_form as launched (read with
+ * k_order 2), cout columns, operand dtype (negative: not known).  0 = the library's choice, where nothing fits; never an error. */
+int hmmr_conv_tile_for(int k_order, int filter_1x1, int conv3_form, int cout, int dtype, int candidate);
+/* The next two are part of the ABI like every other entry point, to stay: the fit rule is exported so that the host tests can hold
+ * hmmr_conv_tile_for's answers against it, the f_movie tile so that the C packer and the Python packer read one constant.
+ * The fit rule every dispatcher of hmmr_conv_gemm asks before it queues anything: does `tile` (not 0) take a problem of that kind?  cout, win (image
+ * width) and ksteps (1x1 stream: (cin + cin2) / 16) of 0 and a negative dtype are "not known, not checked".  0, or -1 with the reason in hmmr_last_error. */
+int hmmr_conv_tile_fits(int tile, int k_order, int filter_1x1, int conv3_form, int cout, int dtype, int win, int ksteps);
+/* the tile the packers give the f_movie convolutions of a split model */
+int hmmr_conv_tile_f_movie(void);
 
 int hmmr_conv_gemm(const hmmr_conv_desc_t* d, void* stream);
 size_t hmmr_conv_splitk_workspace_bytes(int m, int cout, int split_k);

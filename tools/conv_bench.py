@@ -40,7 +40,7 @@ def run(lib, name, n, h, cin, cout, k, stride, kind, dt, tile, iters=20):
     d.in_img_stride, d.in_row_stride, d.in_px_stride = h * h * cin, h * cin, cin
     d.kh = d.kw = k; d.sy = d.sx = stride; d.py = d.px = pad
     d.ho = d.wo = ho; d.cout = cout; d.ldo = cout; d.tile = tile
-    if tile in (9, 10, 11):
+    if tile in PATCH:
         d.k_order = 1        # the 3x3 patch kernel (timing only: the random filter needs no re-packing)
     keep = [x, w, sc, sh, out]
     nbytes = x.numel() * x.element_size() / (stride * stride if k == 1 else 1) + out.numel() * out.element_size()
@@ -98,10 +98,12 @@ SHAPES = [  # name, h, cin, cout, k, stride, kind
 
 
 TILES = (1, 5, 2, 6, 3)
+PATCH = ()                # the patch family's tile numbers (set in main())
 
 
 def main():
-    global TILES
+    global TILES, PATCH
+    PATCH = [r.tile for r in L.conv_tiles(L.TILE_PATCH)]
     if len(sys.argv) > 3:
         TILES = tuple(int(t) for t in sys.argv[3].split(','))
     only = sys.argv[4].split(',') if len(sys.argv) > 4 else None
@@ -115,9 +117,9 @@ def main():
         if only and not any(o in name for o in only):
             continue
         for tile in TILES:
-            if (tile in (1, 5, 7, 9, 11) and cout % 128) or (tile in (8, 10) and cout % 256):
+            if lib.hmmr_conv_tile_for(int(tile in PATCH), 0, 0, cout, L.HMMR_F16X3, tile) != tile:      # the tuner's column rule
                 continue
-            if tile in (9, 10, 11) and not (k == 3 and stride == 1 and dt in ("f16x3", "split")):
+            if tile in PATCH and not (k == 3 and stride == 1 and dt in ("f16x3", "split")):
                 continue
             rows.append(run(lib, name, n, h, cin, cout, k, stride, kind, dt, tile))
             print(json.dumps(rows[-1]), flush=True)

@@ -26,7 +26,7 @@ SHAPES = [  # name, h, cin, cout, n_split (or: "c3", cin2, res, out2 -- the conv
 
 def main():
     n = int(sys.argv[1]) if len(sys.argv) > 1 else 257
-    tiles = [int(t) for t in sys.argv[2].split(",")] if len(sys.argv) > 2 else [0, 22, 23, 24, 25]
+    tiles = [int(t) for t in sys.argv[2].split(",")] if len(sys.argv) > 2 else [0] + [r.tile for r in L.conv_tiles(L.TILE_STREAM_1X1)]
     k_order = int(sys.argv[3]) if len(sys.argv) > 3 else 2
     lib = L.load()
     dev = torch.device("cuda:0")

@@ -19,10 +19,9 @@ if "probe" in L.LIB_PATH:
     lib.hmmr_set_debug(C.byref(d_))
 blk = sys.argv[1] if len(sys.argv) > 1 else "b3"
 n = int(sys.argv[2]) if len(sys.argv) > 2 else 257
-tiles = [int(t) for t in sys.argv[3:]] or [12, 13, 14, 15, 16, 17, 18]
 cch, hw = {"b1": (64, 56), "b2": (128, 28), "b3": (256, 14), "b4": (512, 7)}[blk]
-if blk == "b1" and len(sys.argv) <= 3:
-    tiles = [19, 20]
+INFO = {r.tile: r for r in L.conv_tiles(L.TILE_STREAM_3X3)}
+tiles = [int(t) for t in sys.argv[3:]] or [t for t, r in INFO.items() if r.narrow == (cch == 64)]      # every tile that takes the block's columns
 dev = "cuda"
 X3 = L.HMMR_F16X3
 g = torch.Generator(device="cpu").manual_seed(5)
@@ -70,7 +69,7 @@ def run(k_order, tile, reps=10):
     torch.cuda.synchronize()
     ms = e0.elapsed_time(e1) / reps
     if ts is not None and k_order == 2:
-        bm = {12: 448, 13: 256, 14: 512, 15: 384, 16: 320, 17: 512, 18: 384, 19: 640, 20: 512, 21: 224}[tile]
+        bm = INFO[tile].pixels
         nb = ((n * hw * hw + bm - 1) // bm) * max(1, cch // 128)
         t = ts[:nb].cpu().numpy().astype(np.float64)
         t0 = t[:, :, 0].min()
