@@ -112,6 +112,11 @@ extern "C" int hmmr_ief_fwd_from(const hmmr_ief_weights_t* w, const float* strip
     HMMR_REQUIRE(m > 0, "hmmr_ief_fwd: m must be positive");
     HMMR_REQUIRE(w->num_regressors >= 1 && w->num_regressors <= HMMR_MAX_REGRESSORS, "hmmr_ief_fwd: bad num_regressors");
     HMMR_REQUIRE(w->reg[0].nd == 85, "hmmr_ief_fwd: regressor 0 must predict 85-D omega");
+    // (every refusal comes before the first launch: the operand cast below is one)
+    const int nd_delta = w->no_optcam ? 75 : 72;               // models.py:333-336
+    for (int r = 0; r < w->num_regressors; ++r)
+        HMMR_REQUIRE(w->reg[r].nd == (r == 0 ? 85 : nd_delta), "hmmr_ief_fwd: regressor %d has nd=%d (expected %d)", r,
+                     w->reg[r].nd, r == 0 ? 85 : nd_delta);
     const IefBufs L = ief_layout(m, w->dtype, w->num_regressors - 1);
     HMMR_REQUIRE(ws_bytes >= L.total, "hmmr_ief_fwd: workspace too small");
     hipStream_t s = (hipStream_t)stream;
@@ -132,10 +137,6 @@ extern "C" int hmmr_ief_fwd_from(const hmmr_ief_weights_t* w, const float* strip
     float* th[2] = {(float*)(base + L.th[0]), (float*)(base + L.th[1])};
     const unsigned gth = (unsigned)(((long long)m * LDT + 255) / 256);
     const unsigned gfin = (unsigned)(((long long)m * 85 + 255) / 256);
-    const int nd_delta = w->no_optcam ? 75 : 72;               // models.py:333-336
-    for (int r = 0; r < w->num_regressors; ++r)
-        HMMR_REQUIRE(w->reg[r].nd == (r == 0 ? 85 : nd_delta), "hmmr_ief_fwd: regressor %d has nd=%d (expected %d)", r,
-                     w->reg[r].nd, r == 0 ? 85 : nd_delta);
     // The delta regressors are independent of each other (each starts from the present prediction, models.py:343-361)
     // and of one shape: they run as ONE grouped launch per layer when their operands lie at one common stride (always
     // true for two of them; the packer allocates more of them evenly).  Same kernels on the same operands: same bits.

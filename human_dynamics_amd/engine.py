@@ -404,43 +404,55 @@ class HmmrEngine(object):
             self._side_streams.append(torch.cuda.Stream(device=self.device, priority=int(devflags.get("RESNET_PRIORITY"))))
         return self._side_streams[i]
 
-    def temporal(self, phi):
-        """phi [b,t,2048] fp32 -> movie strips [b,t,2048].  az_fc2_groupnorm, src/models.py:121-141."""
+    def _out(self, out, shape, dtype=torch.float32):
+        """the output of a stage call: a fresh tensor, or the caller's (contiguous, on this device, at least `shape` along axis 0:
+        its first rows are written and returned)"""
+        if out is None:
+            return torch.empty(shape, dtype=dtype, device=self.device)
+        assert out.is_cuda and out.device == self.device and out.dtype == dtype and out.is_contiguous(), "out: a contiguous device tensor"
+        assert out.dim() == len(shape) and out.shape[0] >= shape[0] and tuple(out.shape[1:]) == tuple(shape[1:]), (tuple(out.shape), shape)
+        return out[:shape[0]]
+
+    def temporal(self, phi, out=None):
+        """phi [b,t,2048] fp32 -> movie strips [b,t,2048] (into the first b windows of `out`, if given).  az_fc2_groupnorm,
+        src/models.py:121-141."""
         self._need(self.tw, "AZ_FC_block*")
         phi = self.to_device(phi)
         b, t, c = phi.shape
         assert c == 2048
-        out = torch.empty_like(phi)
+        out = self._out(out, (b, t, c))
         nbytes = self.lib.hmmr_temporal_workspace_bytes(b, t, self.temporal_dtype)
         ws = self._ws["temporal"].get(nbytes)
         L.check(self.lib.hmmr_temporal_fwd(C.byref(self.tw), phi.data_ptr(), b, t, out.data_ptr(),
                                            ws.data_ptr(), nbytes, self._stream()), "hmmr_temporal_fwd")
         return out
 
-    def hallucinate(self, phi):
-        """phi [..., 2048] -> hallucinated movie strips, same shape.  fc2_res, src/models.py:270-296."""
+    def hallucinate(self, phi, out=None):
+        """phi [..., 2048] -> hallucinated movie strips, same shape (out: [>= rows, 2048], its first rows are written).  fc2_res,
+        src/models.py:270-296."""
         if self.hw is None:
             raise L.HmmrError("the loaded weights have no fc2_res/* variables (pred_mode 'hal')")
         phi = self.to_device(phi)
         flat = phi.reshape(-1, 2048)
         m = flat.shape[0]
-        out = torch.empty_like(flat)
+        out = self._out(out, (m, 2048))
         nbytes = self.lib.hmmr_hallucinator_workspace_bytes(m, self.temporal_dtype)
         ws = self._ws["hal"].get(nbytes)
         L.check(self.lib.hmmr_hallucinator_fwd(C.byref(self.hw), flat.data_ptr(), m, out.data_ptr(),
                                                ws.data_ptr(), nbytes, self._stream()), "hmmr_hallucinator_fwd")
         return out.reshape(phi.shape)
 
-    def ief(self, strips, omega_start=None, use_delta_from_pred=True):
+    def ief(self, strips, omega_start=None, use_delta_from_pred=True, out=None):
         """strips [m,2048] -> omegas [R,m,85]; R = 1 + len(delta_t_values), deltas in sorted order.
         batch_pred_omega / call_hmr_ief, src/models.py:233-267, 299-377.  omega_start: [m,85] starting point of the IEF
         (`omega_mean`; None = the checkpoint's mean theta in every row, tester.py:181).  use_optcam is a property of the
-        packed delta regressors (72- or 75-wide, `self.use_optcam`)."""
+        packed delta regressors (72- or 75-wide, `self.use_optcam`).  out: a flat fp32 tensor of at least R * m * 85 floats; its
+        head is written and returned as [R,m,85]."""
         self._need(self.iw, "single_view_ief*/3D_module/* and mean_param")
         strips = self.to_device(strips)
         m = strips.shape[0]
         R = self.iw.num_regressors
-        out = torch.empty((R, m, 85), dtype=torch.float32, device=self.device)
+        out = self._out(out, (R * m * 85,)).view(R, m, 85)
         nbytes = self.lib.hmmr_ief_workspace_bytes(m, R, self.ief_dtype)
         ws = self._ws["ief"].get(nbytes)
         start = None
@@ -517,11 +529,13 @@ class HmmrEngine(object):
         L.check(self.lib.hmmr_smpl_fwd_records(C.byref(self.sc), om.data_ptr(), R, n, rec.data_ptr(), rec.stride(0), offs,
                                                ws.data_ptr(), nbytes, self._stream()), "hmmr_smpl_fwd_records")
 
-    def groupnorm_relu(self, x, gamma, beta, groups=32, out_dtype=L.HMMR_F32):
+    def groupnorm_relu(self, x, gamma, beta, groups=32, out_dtype=L.HMMR_F32, out=None):
+        """x [b,t,c] fp32 -> relu(group_norm) [b,t,c] in the storage type of `out_dtype` (packing.act_to_f32 reads it); out: a tensor of
+        that storage type with at least b windows, its first b are written"""
         x = self.to_device(x)
         b, t, c = x.shape
         g, be = self.to_device(gamma), self.to_device(beta)
-        out = packing.empty_act((b, t, c), out_dtype, self.device)
+        out = self._out(out, (b, t, c), packing.empty_act((0,), out_dtype, "cpu").dtype)
         L.check(self.lib.hmmr_groupnorm_relu(x.data_ptr(), g.data_ptr(), be.data_ptr(), b, t, c, groups,
                                              out.data_ptr(), out_dtype, self._stream()), "hmmr_groupnorm_relu")
         return out

@@ -383,3 +383,84 @@ def test_smpl_entries_refuse_before_anything_is_queued():
         refused(records(offs=offs), b"field offset outside the record")
     refused(records(sc=consts(vpad=320)), b"vpad=320")
     refused(records(sc=consts(lbs_nnz=25)), b"lbs_nnz=25")
+
+
+def test_tail_entries_refuse_before_anything_is_queued():
+    """hmmr_groupnorm_relu, hmmr_temporal_fwd, hmmr_hallucinator_fwd, hmmr_ief_fwd_from: every refusal, with dummy (never dereferenced)
+    pointers and no device -- each is a -1 with a message, the status of a check in front of the first launch (a call that got past
+    its checks would have to launch; a failed launch is -2).  The valid calls are what tests/test_gpu_tail.py sweeps."""
+    import ctypes as C
+    lib = _lib.load()
+    P = [0x10000 * (i + 1) for i in range(8)]
+    BIG = 1 << 40
+    DTYPES = (_lib.HMMR_F32, _lib.HMMR_BF16, _lib.HMMR_F16X3)
+
+    def refused(rc, *words):
+        msg = lib.hmmr_last_error()
+        assert rc == -1 and msg, (rc, msg)
+        for w in words:
+            assert w in msg, (w, msg)
+
+    def gn(x=P[0], gamma=P[1], beta=P[2], b=2, t=7, c=2048, groups=32, out=P[3], dt=_lib.HMMR_F32):
+        return lib.hmmr_groupnorm_relu(x, gamma, beta, b, t, c, groups, out, dt, None)
+
+    for missing in ("x", "gamma", "beta", "out"):
+        refused(gn(**{missing: None}), b"hmmr_groupnorm_relu", b"null argument")
+    for kw in (dict(b=0), dict(b=-1), dict(t=0), dict(t=-2), dict(groups=0), dict(groups=-4)):
+        refused(gn(**kw), b"hmmr_groupnorm_relu", b"bad shape")
+    for c, groups in ((2048, 31), (128, 32), (2048, 512), (2052, 513), (96, 8), (100, 10)):      # no whole groups, or 4 / 12 / 10 channels each
+        refused(gn(c=c, groups=groups), b"multiple of 8")
+    for dt in (3, -1):
+        refused(gn(dt=dt), b"bad dtype")
+
+    def temporal(dt=_lib.HMMR_F32, blocks=3, w=True, phi=P[0], b=2, t=7, strips=P[1], ws=P[2], ws_bytes=BIG):
+        tw = _lib.TemporalWeights()
+        tw.dtype, tw.num_blocks = dt, blocks
+        return lib.hmmr_temporal_fwd(C.byref(tw) if w else None, phi, b, t, strips, ws, ws_bytes, None)
+
+    def hal(dt=_lib.HMMR_F32, w=True, phi=P[0], m=5, out=P[1], ws=P[2], ws_bytes=BIG):
+        hw = _lib.HallucinatorWeights()
+        hw.dtype = dt
+        return lib.hmmr_hallucinator_fwd(C.byref(hw) if w else None, phi, m, out, ws, ws_bytes, None)
+
+    def ief(dt=_lib.HMMR_F32, R=3, nd=(85, 72, 72, 72, 72, 72, 72, 72), no_optcam=0, w=True, strips=P[0], start=None, m=5, omegas=P[1],
+            ws=P[2], ws_bytes=BIG):
+        iw = _lib.IefWeights()
+        iw.dtype, iw.num_regressors, iw.num_stages, iw.no_optcam, iw.mean_theta = dt, R, 3, no_optcam, P[3]
+        for r in range(_lib.MAX_REGRESSORS):
+            iw.reg[r].nd = nd[r]
+        return lib.hmmr_ief_fwd_from(C.byref(iw) if w else None, strips, start, m, omegas, ws, ws_bytes, None)
+
+    for dt in DTYPES:
+        refused(temporal(dt, w=False), b"hmmr_temporal_fwd", b"null argument")
+        for missing in ("phi", "strips", "ws"):
+            refused(temporal(dt, **{missing: None}), b"hmmr_temporal_fwd", b"null argument")
+        for kw in (dict(b=0), dict(b=-1), dict(t=0), dict(t=-1)):
+            refused(temporal(dt, **kw), b"hmmr_temporal_fwd", b"bad shape")
+        for blocks in (0, -1, _lib.MAX_TEMPORAL_BLOCKS + 1):
+            refused(temporal(dt, blocks=blocks), b"bad num_blocks")
+        refused(temporal(dt, ws_bytes=lib.hmmr_temporal_workspace_bytes(2, 7, dt) - 1), b"workspace too small")
+
+        refused(hal(dt, w=False), b"hmmr_hallucinator_fwd", b"null argument")
+        for missing in ("phi", "out", "ws"):
+            refused(hal(dt, **{missing: None}), b"hmmr_hallucinator_fwd", b"null argument")
+        for m in (0, -1):
+            refused(hal(dt, m=m), b"m must be positive")
+        refused(hal(dt, ws_bytes=lib.hmmr_hallucinator_workspace_bytes(5, dt) - 1), b"workspace too small")
+
+        refused(ief(dt, w=False), b"hmmr_ief_fwd", b"null argument")
+        for missing in ("strips", "omegas", "ws"):
+            refused(ief(dt, **{missing: None}), b"hmmr_ief_fwd", b"null argument")
+        for m in (0, -1):
+            refused(ief(dt, m=m), b"m must be positive")
+        for R in (0, -1, _lib.MAX_REGRESSORS + 1):
+            refused(ief(dt, R=R), b"bad num_regressors")
+        for nd0 in (72, 75, 0, 86):
+            refused(ief(dt, nd=(nd0,) + (72,) * 7), b"regressor 0 must predict 85-D omega")
+        # a delta width that contradicts no_optcam: 75-wide regressors in a use_optcam struct and the reverse, one odd one among eight
+        refused(ief(dt, nd=(85,) + (75,) * 7), b"regressor 1 has nd=75 (expected 72)")
+        refused(ief(dt, nd=(85,) + (72,) * 7, no_optcam=1), b"regressor 1 has nd=72 (expected 75)")
+        refused(ief(dt, R=8, nd=(85,) + (72,) * 6 + (75,)), b"regressor 7 has nd=75 (expected 72)")
+        refused(ief(dt, R=2, nd=(85, 85) + (72,) * 6), b"regressor 1 has nd=85")
+        refused(ief(dt, ws_bytes=lib.hmmr_ief_workspace_bytes(5, 3, dt) - 1), b"workspace too small")
+        refused(ief(dt, start=P[4], ws_bytes=lib.hmmr_ief_workspace_bytes(5, 3, dt) - 1), b"workspace too small")
