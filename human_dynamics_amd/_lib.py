@@ -156,6 +156,11 @@ class SmplConsts(C.Structure):
                 ("dirs_split", _vp)]
 
 
+class SmplGradConsts(C.Structure):
+    """hmmr_smpl_grad_consts_t: what hmmr_smpl_bwd needs beside SmplConsts (the keypoint regressor by vertex)"""
+    _fields_ = [("num_verts", C.c_int), ("num_kps", C.c_int), ("vk_ptr", _ip), ("vk_idx", _ip), ("vk_val", _fp)]
+
+
 class Var(C.Structure):
     """hmmr_var_t: one checkpoint variable for the C-side packers (csrc/pack.cpp)"""
     _fields_ = [("name", C.c_char_p), ("data", _fp), ("numel", C.c_int64)]
@@ -258,6 +263,8 @@ SIGNATURES = {
     "hmmr_pack_ief": (C.c_int, [C.POINTER(Var), C.c_int, C.c_int, C.POINTER(C.c_int), C.c_int, C.c_int, _vp, C.c_size_t, _vp, C.POINTER(IefWeights)]),
     "hmmr_pack_smpl_bytes": (C.c_size_t, [C.POINTER(SmplSource), C.c_int, C.c_int]),
     "hmmr_pack_smpl": (C.c_int, [C.POINTER(SmplSource), C.c_int, C.c_int, _vp, C.c_size_t, _vp, C.POINTER(SmplConsts)]),
+    "hmmr_pack_smpl_grad_bytes": (C.c_size_t, [C.POINTER(SmplSource), C.c_int]),
+    "hmmr_pack_smpl_grad": (C.c_int, [C.POINTER(SmplSource), C.c_int, _vp, C.c_size_t, _vp, C.POINTER(SmplGradConsts)]),
     "hmmr_last_error": (C.c_char_p, []),
     "hmmr_run_flags": (C.c_int, [C.POINTER(C.c_uint), C.c_int]),
     "hmmr_set_debug": (None, [C.POINTER(Debug)]),
@@ -287,6 +294,9 @@ SIGNATURES = {
     "hmmr_smpl_workspace_bytes": (C.c_size_t, [C.c_int]),
     "hmmr_smpl_fwd": (C.c_int, [C.POINTER(SmplConsts), _fp, C.c_int, _fp, C.c_int, _fp, C.c_int, C.c_int,
                                 _fp, _fp, _fp, _fp, _vp, C.c_size_t, _vp]),
+    "hmmr_smpl_bwd_workspace_bytes": (C.c_size_t, [C.POINTER(SmplConsts), C.c_int]),
+    "hmmr_smpl_bwd": (C.c_int, [C.POINTER(SmplConsts), C.POINTER(SmplGradConsts), _fp, C.c_int, _fp, C.c_int, _fp, C.c_int, _fp, C.c_int,
+                                _fp, _fp, _fp, _fp, _fp, _fp, _fp, _vp, C.c_size_t, _vp]),
     "hmmr_crop_frames": (C.c_int, [_vp, _ip, C.c_int, C.c_int, C.c_int, _fp, _vp]),
     "hmmr_tube_augment": (C.c_int, [_vp, C.c_int, C.c_int, C.c_int, C.c_int, _ip, _vp, _fp, C.c_int, _fp, _vp]),
     "hmmr_track_workspace_bytes": (C.c_size_t, [C.c_int, C.c_int]),

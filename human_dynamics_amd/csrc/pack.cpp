@@ -706,6 +706,28 @@ void pack_smpl(const hmmr_smpl_source_t* s, int lsp, int split, Blob& b, hmmr_sm
     sc->kreg_val = put_f32(b, kval.data(), kval.size(), kval.size());
 }
 
+// keypoint regressor [nv][K] -> CSR by vertex (the transpose of pack_smpl's CSR by keypoint): what the backward's vertex pass walks
+void pack_smpl_grad(const hmmr_smpl_source_t* s, int lsp, Blob& b, hmmr_smpl_grad_consts_t* gc) {
+    memset(gc, 0, sizeof(*gc));
+    const int nv = s->num_verts, nkall = s->num_kps;
+    if (nv < 1 || nkall < 1 || !s->kp_regressor) fail("incomplete source");
+    const int nk = lsp ? (nkall < 14 ? nkall : 14) : nkall;           // batch_smpl.py:81-82
+    std::vector<int32_t> vptr(1, 0), vidx;
+    std::vector<float> vval;
+    for (int vv = 0; vv < nv; ++vv) {
+        for (int k = 0; k < nk; ++k) {
+            const float x = s->kp_regressor[(size_t)vv * nkall + k];
+            if (x != 0.f) { vidx.push_back(k); vval.push_back(x); }
+        }
+        vptr.push_back((int32_t)vidx.size());
+    }
+    if (vidx.empty()) { vidx.push_back(0); vval.push_back(0.f); }
+    gc->num_verts = nv; gc->num_kps = nk;
+    gc->vk_ptr = put_i32(b, vptr.data(), vptr.size());
+    gc->vk_idx = put_i32(b, vidx.data(), vidx.size());
+    gc->vk_val = put_f32(b, vval.data(), vval.size(), vval.size());
+}
+
 template <typename F> int guarded(const char* what, Blob& b, F&& f) {
     try { f(); }
     catch (const PackError& e) { hmmr_set_error("%s: %s", what, e.msg.c_str()); return -1; }
@@ -768,4 +790,14 @@ extern "C" int hmmr_pack_smpl(const hmmr_smpl_source_t* src, int lsp, int split,
     if (!src || !host_blob || !out) { hmmr_set_error("hmmr_pack_smpl: null argument"); return -1; }
     Blob b(host_blob, blob_bytes, device_base);
     return guarded("hmmr_pack_smpl", b, [&] { pack_smpl(src, lsp, split, b, out); });
+}
+extern "C" size_t hmmr_pack_smpl_grad_bytes(const hmmr_smpl_source_t* src, int lsp) {
+    if (!src) return 0;
+    return counted("hmmr_pack_smpl_grad_bytes", [&](Blob& b) { hmmr_smpl_grad_consts_t t; pack_smpl_grad(src, lsp, b, &t); });
+}
+extern "C" int hmmr_pack_smpl_grad(const hmmr_smpl_source_t* src, int lsp, void* host_blob, size_t blob_bytes, const void* device_base,
+                                   hmmr_smpl_grad_consts_t* out) {
+    if (!src || !host_blob || !out) { hmmr_set_error("hmmr_pack_smpl_grad: null argument"); return -1; }
+    Blob b(host_blob, blob_bytes, device_base);
+    return guarded("hmmr_pack_smpl_grad", b, [&] { pack_smpl_grad(src, lsp, b, out); });
 }

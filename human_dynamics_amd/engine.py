@@ -148,6 +148,7 @@ class HmmrEngine(object):
         # stays on fp32 operands too, so nothing in it can clamp
         all_f32 = (self.dtype, self.temporal_dtype, self.ief_dtype) == (L.HMMR_F32,) * 3
         self.sc = packing.pack_smpl(smpl, self.store, joint_type, split=not all_f32) if smpl is not None else None
+        self._smpl_source, self.joint_type, self._gc = smpl, joint_type, None     # the backward's constants: packed on first use (smpl_backward)
         self.num_kps = self.sc.num_kps if self.sc is not None else assets.NUM_KPS
         self.num_verts = self.sc.num_verts if self.sc is not None else assets.NUM_VERTS
         self._ws = {k: _Workspace(self.device) for k in ("resnet", "temporal", "ief", "smpl", "hal")}   # + "resnet<i>" per side stream
@@ -498,6 +499,46 @@ class HmmrEngine(object):
                                        verts.data_ptr(), joints.data_ptr(), L.ptr(kps), L.ptr(rs),
                                        ws.data_ptr(), nbytes, self._stream()), "hmmr_smpl_fwd")
         return verts, joints, kps, rs
+
+    def smpl_backward(self, theta, beta, cams=None, joints=None, d_verts=None, d_joints=None, d_kps=None, d_rs=None, want_cams=None):
+        """The derivative of `smpl` (hmmr_smpl_bwd, csrc/smpl_grad.hip): theta [m,72], beta [m,10], cams [m,3] or None as the forward
+        took them (fp32 device tensors; row-major views with a unit inner stride are used in place), joints [m,K,3] = the forward's
+        output (needed with d_kps), and the gradients of a loss with respect to verts [m,V,3], joints [m,K,3], kps [m,K,2] and
+        Rs [m,24,3,3] -- any of them None (= zero), at least one given.  Returns d_theta [m,72], d_beta [m,10] and d_cams [m,3]
+        (None without cams, or with want_cams=False).  The function differentiated is the exact fp32 forward."""
+        def prep(x, width):
+            if not (isinstance(x, torch.Tensor) and x.is_cuda and x.dtype == torch.float32
+                    and x.dim() == 2 and x.stride(1) == 1 and x.shape[1] == width):
+                x = self.to_device(x).reshape(-1, width)
+            return x
+        theta, beta = prep(theta, 72), prep(beta, 10)
+        m = theta.shape[0]
+        cams = prep(cams, 3) if cams is not None else None
+        V, K = self.num_verts, self.num_kps
+
+        def dense(x, shape):
+            if x is None:
+                return None
+            x = self.to_device(x)
+            if tuple(x.shape) != (m,) + shape:
+                raise ValueError("expected a gradient of shape %s, got %s" % ((m,) + shape, tuple(x.shape)))
+            return x
+        joints, d_verts, d_joints = dense(joints, (K, 3)), dense(d_verts, (V, 3)), dense(d_joints, (K, 3))
+        d_kps, d_rs = dense(d_kps, (K, 2)), dense(d_rs, (24, 3, 3))
+        if self._gc is None:                                 # packed on the first backward call: an inference-only process never pays for it
+            self._gc = packing.pack_smpl_grad(self._smpl_source, self.store, self.joint_type)
+        want_cams = (cams is not None) if want_cams is None else (bool(want_cams) and cams is not None)
+        d_theta = torch.empty((m, 72), dtype=torch.float32, device=self.device)
+        d_beta = torch.empty((m, 10), dtype=torch.float32, device=self.device)
+        d_cams = torch.empty((m, 3), dtype=torch.float32, device=self.device) if want_cams else None
+        nbytes = self.lib.hmmr_smpl_bwd_workspace_bytes(C.byref(self.sc), m)
+        ws = self._ws.setdefault("smpl_bwd", _Workspace(self.device)).get(nbytes)
+        L.check(self.lib.hmmr_smpl_bwd(C.byref(self.sc), C.byref(self._gc), theta.data_ptr(), theta.stride(0), beta.data_ptr(), beta.stride(0),
+                                       L.ptr(cams), cams.stride(0) if cams is not None else 0, L.ptr(joints), m,
+                                       L.ptr(d_verts), L.ptr(d_joints), L.ptr(d_kps), L.ptr(d_rs),
+                                       d_theta.data_ptr(), d_beta.data_ptr(), L.ptr(d_cams),
+                                       ws.data_ptr(), nbytes, self._stream()), "hmmr_smpl_bwd")
+        return d_theta, d_beta, d_cams
 
     def smpl_into(self, theta, beta, cams, rec, off_verts, off_joints, off_kps, off_rs):
         """SMPL forward that writes instance i's verts/joints/kps/Rs straight into row i of

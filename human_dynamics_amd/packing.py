@@ -693,3 +693,20 @@ def pack_smpl(smpl, store, joint_type="cocoplus", split=True, impl=None):
     sc.kreg_idx = store.put(kidx, torch.int32).data_ptr()
     sc.kreg_val = store.put(kval.astype(np.float32)).data_ptr()
     return sc
+
+
+def pack_smpl_grad(smpl, store, joint_type="cocoplus"):
+    """What hmmr_smpl_bwd needs beside SmplConsts -> SmplGradConsts: cocoplus_regressor as a CSR by vertex (hmmr_pack_smpl_grad; the
+    first 14 columns for joint_type 'lsp', batch_smpl.py:81-82).  A blob of its own: HmmrEngine packs it on the first backward call."""
+    lib = L.load()
+    import ctypes as C
+    kreg = np.ascontiguousarray(smpl["cocoplus_regressor"], np.float32)
+    src = L.SmplSource()
+    src.num_verts, src.num_kps = kreg.shape
+    src.kp_regressor = kreg.ctypes.data
+    gc = L.SmplGradConsts()
+    lsp = int(joint_type == "lsp")
+    _c_pack(store, lib.hmmr_pack_smpl_grad_bytes(C.byref(src), lsp),
+            lambda host, nb, base: lib.hmmr_pack_smpl_grad(C.byref(src), lsp, host, nb, base, C.byref(gc)))
+    del kreg
+    return gc

@@ -105,8 +105,15 @@ class SMPL(object):
 
     def __call__(self, beta, theta, get_skin=False, name=None):
         """beta [N,10], theta [N,72] or [N,24,3] -> joints [N,K,3]
-        (+ verts [N,6890,3], Rs [N,24,3,3] if get_skin), as device tensors."""
+        (+ verts [N,6890,3], Rs [N,24,3,3] if get_skin), as device tensors.  With gradients enabled and a beta or theta that
+        requires grad the call goes through torch.autograd (tf_smpl/autograd.py: hmmr_smpl_bwd is its backward)."""
         e = self.engine
+        if torch.is_grad_enabled() and any(isinstance(x, torch.Tensor) and x.requires_grad for x in (beta, theta)):
+            from .autograd import smpl_apply
+            verts, joints, _, rs = smpl_apply(e, theta, beta)
+            if get_skin:
+                return verts, joints, rs
+            return joints
         theta = e.to_device(theta).reshape(-1, 72)
         beta = e.to_device(beta).reshape(-1, 10)
         verts, joints, _, rs = e.smpl(theta, beta, None, want_rs=True)

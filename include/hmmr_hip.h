@@ -586,6 +586,41 @@ int hmmr_global_rigid_transformation(const float* Rs, const float* Js, const int
                                      float* new_j, float* A, int rotate_base, void* stream);
 
 /* ------------------------------------------------------------------------- *
+ * SMPL backward (additive to ABI 19): the derivative of hmmr_smpl_fwd -- SMPL.__call__ (src/tf_smpl/batch_smpl.py:89-162),
+ * batch_rodrigues / batch_global_rigid_transformation (src/tf_smpl/batch_lbs.py:42-60, 133-194) and batch_orth_proj_idrot
+ * (src/tf_smpl/projection.py:16-29) -- with respect to theta, beta and the camera; what a trainer's losses on kps, joints,
+ * poses and verts need (csrc/smpl_grad.hip).
+ *
+ * The function differentiated is the forward in exact fp32: R = cos I + (1 - cos) r r^T + sin skew(r) with angle = ||theta + 1e-8||
+ * and r = theta / angle (not a unit vector; both carry a derivative), J = j_template + beta . j_shapedirs, FK in index order,
+ * A = [G_R | G_t - G_R J], v_posed = dirs^T [1, beta, R_1..23 - I], verts = sum_j w[v,j] A_j [v_posed; 1], joints = kreg^T verts,
+ * kps = s (joints_xy + t), Rs = R.  A forward that ran its blend product on split-fp16 operands (the default) is differentiated as
+ * this exact function.  Every intermediate is recomputed from theta and beta; `joints` (the forward's output) is read for the
+ * camera gradient only.  No floating-point atomics: per-tile partials, summed in tile order -- the same inputs give the same bytes.
+ * ------------------------------------------------------------------------- */
+typedef struct {
+    int num_verts;                     /* as in the hmmr_smpl_consts_t it goes with */
+    int num_kps;
+    const int32_t* vk_ptr;             /* CSR BY VERTEX of cocoplus_regressor (the first 14 columns for lsp): [num_verts+1] */
+    const int32_t* vk_idx;             /* keypoint ids, ascending per vertex */
+    const float* vk_val;
+} hmmr_smpl_grad_consts_t;
+
+size_t hmmr_smpl_bwd_workspace_bytes(const hmmr_smpl_consts_t* c, int m);   /* 0 for m <= 0 or c == NULL */
+/* theta, beta, cams: the forward's inputs with the forward's row strides (cams NULL: no camera); joints [m,K,3]: the forward's
+ * output, needed iff d_kps.  Upstream gradients d_verts [m,V,3], d_joints [m,K,3], d_kps [m,K,2], d_rs [m,24,3,3]: any of them
+ * may be NULL (= zero, never read), at least one must be given.  Outputs d_theta [m,72], d_beta [m,10], d_cams [m,3] or NULL
+ * (zeros when d_kps is NULL).  Refused before any launch, with a message in hmmr_last_error: a null c, g, theta, beta, d_theta,
+ * d_beta or ws; m <= 0; no upstream gradient; d_kps without cams or joints; d_cams without cams; lbs_nnz outside 1..24; a
+ * workspace below hmmr_smpl_bwd_workspace_bytes(c, m). */
+int hmmr_smpl_bwd(const hmmr_smpl_consts_t* c, const hmmr_smpl_grad_consts_t* g,
+                  const float* theta, int ld_theta, const float* beta, int ld_beta,
+                  const float* cams, int ld_cam, const float* joints, int m,
+                  const float* d_verts, const float* d_joints, const float* d_kps, const float* d_rs,
+                  float* d_theta, float* d_beta, float* d_cams,
+                  void* ws, size_t ws_bytes, void* stream);
+
+/* ------------------------------------------------------------------------- *
  * Crop before the path (process_image, src/evaluation/run_video.py:56-107; resize_img,
  * src/util/common.py:7-14): frames [n,h,w,3] uint8 -> out [n,224,224,3] fp32 in [-1,1].
  * geom [n][4] int32 = {scaled height, scaled width, u0, v0}: floor(h*scale), floor(w*scale) and the
@@ -997,6 +1032,11 @@ typedef struct {
 size_t hmmr_pack_smpl_bytes(const hmmr_smpl_source_t* src, int lsp, int split);
 int hmmr_pack_smpl(const hmmr_smpl_source_t* src, int lsp, int split, void* host_blob, size_t blob_bytes, const void* device_base,
                    hmmr_smpl_consts_t* out);
+/* What hmmr_smpl_bwd needs beside hmmr_smpl_consts_t: kp_regressor by vertex (lsp as above).  A blob of its own, so an
+ * inference-only process never packs it. */
+size_t hmmr_pack_smpl_grad_bytes(const hmmr_smpl_source_t* src, int lsp);
+int hmmr_pack_smpl_grad(const hmmr_smpl_source_t* src, int lsp, void* host_blob, size_t blob_bytes, const void* device_base,
+                        hmmr_smpl_grad_consts_t* out);
 
 /* ------------------------------------------------------------------------- *
  * A whole video through one call (additive to ABI 19): Tester.predict_all_images (src/evaluation/tester.py:260-312).
