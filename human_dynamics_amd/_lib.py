@@ -161,6 +161,20 @@ class SmplGradConsts(C.Structure):
     _fields_ = [("num_verts", C.c_int), ("num_kps", C.c_int), ("vk_ptr", _ip), ("vk_idx", _ip), ("vk_val", _fp)]
 
 
+LOSS_KP, LOSS_KP_OPTCAM, LOSS_JOINTS, LOSS_SMPL, LOSS_CONST, LOSS_SHAPE_PRIOR = 1, 2, 4, 8, 16, 32      # hmmr_seq_loss_desc_t.flags
+LOSS_NAMES = ("e_kp", "e_joints", "e_smpl_pose", "e_smpl_shape", "e_const", "e_shape", "total")              # losses[0..6] (HMMR_L_*)
+LOSS_NO_VISIBLE, LOSS_NOT_FINITE = 1, 2
+
+
+class SeqLossDesc(C.Structure):
+    """hmmr_seq_loss_desc_t: one call of the trainer's loss stage (csrc/losses.hip)"""
+    _fields_ = [("B", C.c_int), ("T", C.c_int), ("K", C.c_int), ("delta_t", C.c_int), ("flags", C.c_uint), ("weights", C.c_float * 6),
+                ("kps_pred", _fp), ("joints_pred", _fp), ("rs_pred", _fp), ("beta_pred", _fp), ("ld_beta", C.c_int),
+                ("kps_gt", _fp), ("joints_gt", _fp), ("rs_gt", _fp), ("shapes_gt", _fp), ("has_gt3d_smpl", _fp), ("has_gt3d_joints", _fp),
+                ("losses", _fp), ("d_kps", _fp), ("d_joints", _fp), ("d_rs", _fp), ("d_beta", _fp), ("best_cam", _fp), ("status", _vp),
+                ("ws", _vp), ("ws_bytes", C.c_size_t)]
+
+
 class Var(C.Structure):
     """hmmr_var_t: one checkpoint variable for the C-side packers (csrc/pack.cpp)"""
     _fields_ = [("name", C.c_char_p), ("data", _fp), ("numel", C.c_int64)]
@@ -297,6 +311,11 @@ SIGNATURES = {
     "hmmr_smpl_bwd_workspace_bytes": (C.c_size_t, [C.POINTER(SmplConsts), C.c_int]),
     "hmmr_smpl_bwd": (C.c_int, [C.POINTER(SmplConsts), C.POINTER(SmplGradConsts), _fp, C.c_int, _fp, C.c_int, _fp, C.c_int, _fp, C.c_int,
                                 _fp, _fp, _fp, _fp, _fp, _fp, _fp, _vp, C.c_size_t, _vp]),
+    "hmmr_seq_losses_workspace_bytes": (C.c_size_t, [C.c_int, C.c_int]),
+    "hmmr_seq_losses": (C.c_int, [C.POINTER(SeqLossDesc), _vp]),
+    "hmmr_omega_loss_grad_workspace_bytes": (C.c_size_t, [C.POINTER(SmplConsts), C.c_int, C.c_int]),
+    "hmmr_omega_loss_grad": (C.c_int, [C.POINTER(SmplConsts), C.POINTER(SmplGradConsts), C.POINTER(SeqLossDesc), _fp, C.c_int, _fp, _fp,
+                                       _vp, C.c_size_t, _vp]),
     "hmmr_crop_frames": (C.c_int, [_vp, _ip, C.c_int, C.c_int, C.c_int, _fp, _vp]),
     "hmmr_tube_augment": (C.c_int, [_vp, C.c_int, C.c_int, C.c_int, C.c_int, _ip, _vp, _fp, C.c_int, _fp, _vp]),
     "hmmr_track_workspace_bytes": (C.c_size_t, [C.c_int, C.c_int]),

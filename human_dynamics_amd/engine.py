@@ -540,6 +540,97 @@ class HmmrEngine(object):
                                        ws.data_ptr(), nbytes, self._stream()), "hmmr_smpl_bwd")
         return d_theta, d_beta, d_cams
 
+    # -- the trainer's losses (csrc/losses.hip) -----------------------------------
+    def _loss_desc(self, B, T, K, flags, weights, delta_t, gt):
+        """hmmr_seq_loss_desc_t with shape, selection and ground truth filled in; `gt`: {kps, joints, rs, shapes, has_gt3d_smpl,
+        has_gt3d_joints} of fp32 device tensors (missing = NULL).  Returns (desc, the tensors it points to)."""
+        d = L.SeqLossDesc()
+        d.B, d.T, d.K, d.delta_t, d.flags = int(B), int(T), int(K), int(delta_t), int(flags)
+        w = list(weights) if weights is not None else [1.0] * 5
+        if len(w) not in (5, 6):
+            raise ValueError("weights: (e_kp, e_joints, e_smpl, e_const, e_shape), got %d values" % len(w))
+        d.weights = (C.c_float * 6)(*([float(v) for v in w] + [0.0] * (6 - len(w))))
+        N = d.B * d.T
+        shapes = {"kps": (N, d.K, 3), "joints": (N, 14, 3), "rs": (N, 24, 3, 3), "shapes": (d.B, 10), "has_gt3d_smpl": (d.B,),
+                  "has_gt3d_joints": (d.B,)}
+        keep = {}
+        for k, shp in shapes.items():
+            x = (gt or {}).get(k)
+            if x is None:
+                continue
+            x = self.to_device(x).reshape(shp)
+            keep[k] = x
+            setattr(d, {"kps": "kps_gt", "joints": "joints_gt", "rs": "rs_gt", "shapes": "shapes_gt"}.get(k, k), x.data_ptr())
+        return d, keep
+
+    def seq_losses(self, B, T, flags, gt, kps_pred=None, joints_pred=None, rs_pred=None, beta_pred=None, weights=None, delta_t=0,
+                   want_grads=True, want_best_cam=False, check=False, K=None):
+        """The trainer's loss stage (hmmr_seq_losses): predictions as `smpl` returns them for N = B T sequence-major rows (kps_pred
+        [N,K,2], joints_pred [N,K,3], rs_pred [N,24,3,3], beta_pred [N,10] -- a view with a row stride is used in place), `gt` a dict of
+        kps [N,K,3], joints [N,14,3], rs [N,24,3,3], shapes [B,10], has_gt3d_smpl [B], has_gt3d_joints [B]; `flags` a mask of
+        _lib.LOSS_*, `weights` = (e_kp, e_joints, e_smpl, e_const, e_shape).  Returns {losses [8] (order _lib.LOSS_NAMES), d_kps,
+        d_joints, d_rs, d_beta (want_grads: the gradients of total = sum w_i L_i; a bool, or the set of names wanted), best_cam
+        [N,3] (want_best_cam; rows outside an optcam slice are NaN), status (a device int32 word)}.  check=True reads the status back
+        (synchronises) and raises on a frame without a visible keypoint under KP_OPTCAM."""
+        N, K = int(B) * int(T), int(self.num_kps if K is None else K)          # (K: the loss stage alone runs on any keypoint count)
+        d, keep = self._loss_desc(B, T, K, flags, weights, delta_t, gt)
+
+        def dense(x, shape):
+            if x is None:
+                return None
+            x = self.to_device(x)
+            if tuple(x.shape) != shape:
+                raise ValueError("expected a prediction of shape %s, got %s" % (shape, tuple(x.shape)))
+            return x
+        kps_pred, joints_pred, rs_pred = dense(kps_pred, (N, K, 2)), dense(joints_pred, (N, K, 3)), dense(rs_pred, (N, 24, 3, 3))
+        if beta_pred is not None:
+            if not (isinstance(beta_pred, torch.Tensor) and beta_pred.is_cuda and beta_pred.dtype == torch.float32 and beta_pred.dim() == 2
+                    and beta_pred.stride(1) == 1 and beta_pred.shape[1] == 10):
+                beta_pred = self.to_device(beta_pred).reshape(-1, 10)
+            if beta_pred.shape[0] != N:
+                raise ValueError("expected %d rows of beta, got %d" % (N, beta_pred.shape[0]))
+            d.beta_pred, d.ld_beta = beta_pred.data_ptr(), beta_pred.stride(0)
+        d.kps_pred, d.joints_pred, d.rs_pred = L.ptr(kps_pred), L.ptr(joints_pred), L.ptr(rs_pred)
+        names = ("d_kps", "d_joints", "d_rs", "d_beta")
+        wanted = set(names if want_grads is True else (() if not want_grads else want_grads))
+        out = {"losses": torch.empty(8, dtype=torch.float32, device=self.device),
+               "status": torch.zeros(1, dtype=torch.int32, device=self.device)}
+        for k, shp in zip(names, ((N, K, 2), (N, K, 3), (N, 24, 3, 3), (N, 10))):
+            out[k] = torch.empty(shp, dtype=torch.float32, device=self.device) if k in wanted else None
+            setattr(d, k, L.ptr(out[k]))
+        out["best_cam"] = torch.full((N, 3), float("nan"), dtype=torch.float32, device=self.device) if want_best_cam else None
+        d.losses, d.status, d.best_cam = out["losses"].data_ptr(), out["status"].data_ptr(), L.ptr(out["best_cam"])
+        nbytes = self.lib.hmmr_seq_losses_workspace_bytes(d.B, d.T)
+        ws = self._ws.setdefault("losses", _Workspace(self.device)).get(nbytes)
+        d.ws, d.ws_bytes = ws.data_ptr(), nbytes
+        L.check(self.lib.hmmr_seq_losses(C.byref(d), self._stream()), "hmmr_seq_losses")
+        if check and int(out["status"].item()) & L.LOSS_NO_VISIBLE:
+            raise L.HmmrError("hmmr_seq_losses: a frame of the slice has no visible keypoint under KP_OPTCAM (the loss is not finite)")
+        return out
+
+    def omega_loss_grad(self, omega, B, T, flags, gt, weights=None, delta_t=0, use_optcam=False, want_best_cam=False):
+        """The closed loop (hmmr_omega_loss_grad): omega [B T, 85] (or [B, T, 85]) fp32 -> (losses [8], d_omega of omega's shape, status
+        [1] int32, best_cam [N,3] or None): hmmr_smpl_fwd, hmmr_seq_losses and hmmr_smpl_bwd on one stream out of one workspace."""
+        shape = tuple(omega.shape) if isinstance(omega, torch.Tensor) else None
+        om = self.to_device(omega).reshape(-1, 85)
+        N = int(B) * int(T)
+        if om.shape[0] != N:
+            raise ValueError("expected %d rows of omega, got %d" % (N, om.shape[0]))
+        d, keep = self._loss_desc(B, T, self.num_kps, flags, weights, delta_t, gt)
+        if self._gc is None:
+            self._gc = packing.pack_smpl_grad(self._smpl_source, self.store, self.joint_type)
+        losses = torch.empty(8, dtype=torch.float32, device=self.device)
+        d_omega = torch.empty((N, 85), dtype=torch.float32, device=self.device)
+        status = torch.zeros(1, dtype=torch.int32, device=self.device)
+        best_cam = torch.full((N, 3), float("nan"), dtype=torch.float32, device=self.device) if want_best_cam else None
+        d.status, d.best_cam = status.data_ptr(), L.ptr(best_cam)
+        nbytes = self.lib.hmmr_omega_loss_grad_workspace_bytes(C.byref(self.sc), d.B, d.T)
+        ws = self._ws.setdefault("omega_loss", _Workspace(self.device)).get(nbytes)
+        L.check(self.lib.hmmr_omega_loss_grad(C.byref(self.sc), C.byref(self._gc), C.byref(d), om.data_ptr(), int(bool(use_optcam)),
+                                              losses.data_ptr(), d_omega.data_ptr(), ws.data_ptr(), nbytes, self._stream()),
+                "hmmr_omega_loss_grad")
+        return losses, (d_omega.reshape(shape) if shape is not None else d_omega), status, best_cam
+
     def smpl_into(self, theta, beta, cams, rec, off_verts, off_joints, off_kps, off_rs):
         """SMPL forward that writes instance i's verts/joints/kps/Rs straight into row i of
         the packed record tensor `rec` [m, rec_len] at the given float offsets

@@ -1,4 +1,4 @@
-"""Mirror of src/omega.py's prediction container for device tensors.
+"""Mirror of src/omega.py's containers for device tensors.
 
 ``OmegasPred`` slices the 85-D omega into cams [0:3], axis-angle pose [3:75]
 and shape [75:85] (src/omega.py:231-235), runs SMPL once per container
@@ -6,6 +6,8 @@ and shape [75:85] (src/omega.py:231-235), runs SMPL once per container
 :318-323).  Unlike the reference the instance registry is per ``Tester`` (a
 list handed in by the owner) instead of a process-global class attribute, and
 ``compute_all_smpl`` evaluates all containers in ONE SMPL launch sequence.
+
+``OmegasGt`` (src/omega.py:161-194) holds a batch's ground truth as the trainer's losses read it (trainer_losses.py).
 """
 from __future__ import annotations
 
@@ -112,3 +114,51 @@ class OmegasPred(object):
 
     def __len__(self):
         return self.length
+
+
+class OmegasGt(object):
+    """Ground-truth container (src/omega.py:161-194): poses_aa [B,T,24,3] (or [B,T,72]), shapes [B,10], joints [B,T,14,3], kps
+    [B,T,K,3] as (x, y, vis), fp32 on the engine's device.  poses_rot comes from the device batch_rodrigues
+    (tf_smpl.batch_lbs), get_shapes() tiles the shapes over T."""
+
+    def __init__(self, config, poses_aa, shapes, joints, kps, batch_size=None, engine=None):
+        from .tf_smpl.batch_lbs import batch_rodrigues
+        from .ops import compute_deltas_batched
+        if engine is None:
+            raise ValueError("OmegasGt needs the engine its tensors live on (engine=)")
+        self.config, self.engine = config, engine
+        self.batch_size = int(batch_size if batch_size else config.batch_size)
+        B = self.batch_size
+        self.poses_aa = engine.to_device(poses_aa).reshape(B, -1, 24, 3)
+        self.length = self.poses_aa.shape[1]
+        self.poses_rot = batch_rodrigues(self.poses_aa.reshape(-1, 3), engine).reshape(B, -1, 24, 3, 3)
+        self.shapes = engine.to_device(shapes).reshape(B, 10)
+        self.joints = engine.to_device(joints).reshape(B, self.length, 14, 3)
+        self.kps = engine.to_device(kps).reshape(B, self.length, -1, 3)
+        self.deltas_rot = compute_deltas_batched(self.poses_rot[:, :-1], self.poses_rot[:, 1:])
+
+    def __len__(self):
+        return self.length
+
+    def get_joints(self, t=None):
+        return self.joints if t is None else self.joints[:, t]
+
+    def get_kps(self, t=None):
+        return self.kps if t is None else self.kps[:, t]
+
+    def get_poses_aa(self, t=None):
+        return self.poses_aa if t is None else self.poses_aa[:, t]
+
+    def get_poses_rot(self, t=None):
+        return self.poses_rot if t is None else self.poses_rot[:, t]
+
+    def get_deltas_rot(self, t=None):
+        return self.deltas_rot if t is None else self.deltas_rot[:, t]
+
+    def get_deltas_aa(self, t=None):
+        raise Exception("No axis-aligned deltas.")
+
+    def get_shapes(self, t=None):
+        if t is None:                                       # B x T x 10 (src/omega.py:186-191)
+            return self.shapes.unsqueeze(1).expand(-1, self.length, -1)
+        return self.shapes

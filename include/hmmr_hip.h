@@ -621,6 +621,108 @@ int hmmr_smpl_bwd(const hmmr_smpl_consts_t* c, const hmmr_smpl_grad_consts_t* g,
                   void* ws, size_t ws_bytes, void* stream);
 
 /* ------------------------------------------------------------------------- *
+ * Trainer losses (additive to ABI 19): the encoder losses of the sequence trainer on precomputed phis
+ * (src/trainer_sequence_fc.py: compute_losses_batched :791-846, compute_losses_deltas :848-953, the shape prior of
+ * compute_losses_prior), built from src/ops.py (compute_loss_e_kp, compute_loss_e_kp_optcam, compute_loss_e_3d,
+ * compute_loss_mse, compute_loss_e_smooth, compute_loss_shape, align_by_pelvis) and src/tf_smpl/projection.py
+ * (batch_orth_proj_optcam, procrustes2d_vis) -- every loss value AND the gradient of total = sum_i weights[i] L_i with respect
+ * to what hmmr_smpl_fwd returned, in the layouts hmmr_smpl_bwd reads (csrc/losses.hip).
+ *
+ * Rows are sequence-major: row n = b T + t, N = B T.
+ *
+ * Frame slices (compute_losses_deltas :867-884).  delta_t = 0: every frame.  delta_t > 0: pred frames [0, T - delta_t) of each
+ * sequence against gt frames [delta_t, T).  delta_t < 0: pred frames [|delta_t|, T) against gt frames [0, T - |delta_t|).  The
+ * slices apply to the kp, joints and smpl terms; e_const and e_shape always see all N rows.  A pred row outside the slice gets
+ * ZERO cotangents from the sliced terms (written, not left).
+ *
+ * e_kp (compute_loss_e_kp; tf.losses.absolute_difference, SUM_BY_NONZERO_WEIGHTS with its safe division):
+ *   sum_i vis_i (|x_gt - x_pred| + |y_gt - y_pred|) / P over the slice, P = the non-zero elements of the broadcast weight
+ *   = 2 #{vis != 0}; 0 when P = 0.  vis is a weight as given, not binarised.  d_kps = w vis sign(pred - gt) / P, sign(0) = 0.
+ * KP_OPTCAM (compute_loss_e_kp_optcam, batch_orth_proj_optcam, procrustes2d_vis), per frame: v = (kps_gt_z > 0); masked means
+ *   mu1 (pred), mu2 (gt); xmu = v (x - mu1), y = v (x_gt - mu2); A = xmu^T xmu + 1e-6 I; scale = trace(A^-1 xmu^T y) / 2 clipped
+ *   to [0.7, 10]; trans = mu2 / scale - mu1; the loss is e_kp on scale (x + trans).  The camera carries NO gradient
+ *   (stop_gradient): d_kps = scale x (that cotangent).  The 2x2 inverse is closed form; every sum runs in fp64 on the fp32 inputs
+ *   and is rounded once.  A frame of the slice without a visible keypoint has no finite answer in the reference (0 / 0) and none
+ *   here: the loss is not finite and HMMR_LOSS_NO_VISIBLE is set in `status`.
+ * e_joints, e_smpl_pose, e_smpl_shape (compute_loss_e_3d, compute_loss_mse, align_by_pelvis): joints = the first 14 predicted
+ *   joints and the 14 gt joints, each minus the midpoint of joints 3 and 2;  0.5 sum_rows w_row sum (a - b)^2 / (D #{w_row != 0}),
+ *   D = 42 (joints), 216 (rotations, the global one included), 10 (shape), w_row = has_gt3d_joints[b] / has_gt3d_smpl[b] (tf_repeat
+ *   over the slice's frames); 0 when no row has a non-zero weight.  The joint cotangent goes back through the alignment (joints 2
+ *   and 3 receive -0.5 sum_k g_k as well); rows 14 .. K-1 of d_joints are zero.
+ * e_const (compute_loss_e_smooth on betas[:, :-1], betas[:, 1:]): 0.5 mean over B (T - 1) 10 values; 0 without gradient for T = 1.
+ * e_shape (compute_loss_shape): mean(beta^2) over the N 10 values.
+ *
+ * Reduction order (no floating-point atomic; the same inputs give the same bytes): every per-frame sum in element order inside
+ * one thread, in fp64; the frames of a sequence in frame order; the sequences in sequence order; one rounding to fp32 per loss.
+ * The normalisers (P and the row counts) are functions of the ground truth alone.
+ * d_beta = ((e_smpl_shape term + e_const term) + e_shape term), formed in fp64 and rounded once.
+ * ------------------------------------------------------------------------- */
+enum { HMMR_LOSS_KP = 1, HMMR_LOSS_KP_OPTCAM = 2, HMMR_LOSS_JOINTS = 4, HMMR_LOSS_SMPL = 8, HMMR_LOSS_CONST = 16,
+       HMMR_LOSS_SHAPE_PRIOR = 32 };
+/* slots of `losses` and of `weights` */
+enum { HMMR_L_KP = 0, HMMR_L_JOINTS = 1, HMMR_L_SMPL_POSE = 2, HMMR_L_SMPL_SHAPE = 3, HMMR_L_CONST = 4, HMMR_L_SHAPE = 5,
+       HMMR_L_TOTAL = 6 };
+enum { HMMR_W_KP = 0, HMMR_W_JOINTS = 1, HMMR_W_SMPL = 2, HMMR_W_CONST = 3, HMMR_W_SHAPE = 4 };
+#define HMMR_LOSS_NO_VISIBLE 1u      /* status: a frame of the slice had no keypoint with z > 0 under KP_OPTCAM */
+#define HMMR_LOSS_NOT_FINITE 2u      /* status: `total` is not finite */
+typedef struct {
+    int B, T, K;                       /* sequences, frames per sequence, keypoints of the forward */
+    int delta_t;                       /* |delta_t| < T */
+    unsigned flags;                    /* HMMR_LOSS_*; KP and KP_OPTCAM exclude each other; SMPL = pose + shape */
+    float weights[6];                  /* HMMR_W_*: the trainer's loss_weights of e_kp, e_joints, e_smpl (pose and shape share it),
+                                          e_const, e_shape; [5] is not read.  The cotangents are those of total = sum w_i L_i */
+    /* predictions: the forward's outputs, N rows */
+    const float* kps_pred;             /* [N,K,2]; under KP_OPTCAM joints[..., :2] (OmegasPred.compute_smpl with cams [1,0,0]) */
+    const float* joints_pred;          /* [N,K,3] */
+    const float* rs_pred;              /* [N,24,3,3] */
+    const float* beta_pred;            /* N rows of 10 with row stride ld_beta */
+    int ld_beta;
+    /* ground truth; whatever no set flag needs may be NULL and is never read */
+    const float* kps_gt;               /* [N,K,3] (x, y, vis): KP, KP_OPTCAM */
+    const float* joints_gt;            /* [N,14,3]: JOINTS */
+    const float* rs_gt;                /* [N,24,3,3]: SMPL */
+    const float* shapes_gt;            /* [B,10] (OmegasGt.get_shapes tiles it over T): SMPL */
+    const float* has_gt3d_smpl;        /* [B] fp32: SMPL */
+    const float* has_gt3d_joints;      /* [B] fp32: JOINTS */
+    /* outputs */
+    float* losses;                     /* [8], HMMR_L_*; [7] = 0; a cleared flag's loss is 0 */
+    float* d_kps;                      /* [N,K,2]   any of the four may be NULL: that term's backward is not wanted.  A given one */
+    float* d_joints;                   /* [N,K,3]   is written in full -- zeros where no set flag reaches it */
+    float* d_rs;                       /* [N,24,3,3] */
+    float* d_beta;                     /* [N,10]: the DIRECT shape gradient (e_smpl_shape, e_const, e_shape), to be added to
+                                          hmmr_smpl_bwd's d_beta */
+    float* best_cam;                   /* [N,3] or NULL: (scale, tx, ty) of the slice's pred rows under KP_OPTCAM; other rows, and
+                                          every row without KP_OPTCAM, are left untouched */
+    unsigned* status;                  /* one device word or NULL, WRITTEN by the call (not sticky): HMMR_LOSS_NO_VISIBLE / _NOT_FINITE */
+    void* ws;                          /* hmmr_seq_losses_workspace_bytes(B, T) */
+    size_t ws_bytes;
+} hmmr_seq_loss_desc_t;
+
+size_t hmmr_seq_losses_workspace_bytes(int B, int T);     /* 0 for B <= 0 or T <= 0 */
+/* Three launches whatever the flags: per-frame partial sums, the sums in order + the normalisers, the cotangents.  Refused
+ * before any launch (-1, message in hmmr_last_error): a null descriptor; B, T or K <= 0; B T > 2^24; K < 14 with
+ * JOINTS; |delta_t| >= T; KP and KP_OPTCAM together; unknown flag bits; a set flag with a NULL operand (KP / KP_OPTCAM: kps_pred,
+ * kps_gt; JOINTS: joints_pred, joints_gt, has_gt3d_joints; SMPL: rs_pred, rs_gt, beta_pred, shapes_gt, has_gt3d_smpl; CONST /
+ * SHAPE_PRIOR: beta_pred); a NULL losses; ld_beta < 10 with beta_pred; a workspace that is NULL or too small. */
+int hmmr_seq_losses(const hmmr_seq_loss_desc_t* d, void* stream);
+
+/* The closed loop omega [B T, 85] -> losses [8], d_omega [B T, 85]: hmmr_smpl_fwd (theta = omega[:, 3:75], beta = omega[:, 75:85]
+ * in place, ld 85), hmmr_seq_losses, hmmr_smpl_bwd (d_verts NULL) and one assembling launch, on one stream out of one workspace.
+ * `gt_and_flags` gives B, T, K (= c->num_kps), delta_t, flags, weights, the ground truth, best_cam and status; its predictions,
+ * its outputs and its workspace are not read.  use_optcam != 0: the forward runs with cams [1, 0, 0] (kps = joints_xy) and
+ * d_omega[:, :3] = 0; otherwise omega[:, :3] are the cams and d_omega[:, :3] = d_cams.  d_omega[:, 3:75] = d_theta;
+ * d_omega[:, 75:85] = d_beta of hmmr_smpl_bwd + d_beta of hmmr_seq_losses (one fp32 addition, in that order).  The result
+ * equals the three separate calls byte for byte.  Workspace, in order (csrc/losses.hip: omega_layout): the forward's, the
+ * backward's and the loss stage's workspaces, cams, verts, joints, kps, Rs, d_kps, d_joints, d_rs, d_beta (direct), d_theta,
+ * d_beta (SMPL), d_cams.  Refused before any launch: a null c, g, omega, losses or d_omega; every refusal of hmmr_seq_losses that
+ * concerns shape, flags, delta_t and the ground truth; K != c->num_kps; and what hmmr_smpl_fwd / hmmr_smpl_bwd refuse of the
+ * constants (lbs_nnz outside 1..24, grad constants of another model, vpad / dirs alignment); a workspace that is NULL or too small. */
+size_t hmmr_omega_loss_grad_workspace_bytes(const hmmr_smpl_consts_t* c, int B, int T);     /* 0 for c == NULL, B <= 0 or T <= 0 */
+int hmmr_omega_loss_grad(const hmmr_smpl_consts_t* c, const hmmr_smpl_grad_consts_t* g, const hmmr_seq_loss_desc_t* gt_and_flags,
+                         const float* omega, int use_optcam, float* losses, float* d_omega,
+                         void* ws, size_t ws_bytes, void* stream);
+
+/* ------------------------------------------------------------------------- *
  * Crop before the path (process_image, src/evaluation/run_video.py:56-107; resize_img,
  * src/util/common.py:7-14): frames [n,h,w,3] uint8 -> out [n,224,224,3] fp32 in [-1,1].
  * geom [n][4] int32 = {scaled height, scaled width, u0, v0}: floor(h*scale), floor(w*scale) and the
