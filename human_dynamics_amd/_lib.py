@@ -149,6 +149,17 @@ class IefWeights(C.Structure):
                 ("no_optcam", C.c_int), ("delta_from_start", C.c_int)]
 
 
+class IefRegGrads(C.Structure):
+    """hmmr_ief_reg_grads_t: one regressor's gradients in the layouts of the HMMR_F32 bank (csrc/ief_grad.hip); each may be NULL"""
+    _fields_ = [(k, _fp) for k in ("d_fc1_phi", "d_fc1_theta", "d_fc2", "d_fc3", "d_b1", "d_b2", "d_b3")]
+
+
+class IefBwdDesc(C.Structure):
+    """hmmr_ief_bwd_desc_t: one call of the IEF backward"""
+    _fields_ = [("strips", _fp), ("omega_start", _fp), ("keep", _vp), ("keep_scale", C.c_float), ("m", C.c_int), ("d_omegas", _fp),
+                ("d_strips", _fp), ("d_omega_start", _fp), ("reg", IefRegGrads * MAX_REGRESSORS)]
+
+
 class SmplConsts(C.Structure):
     _fields_ = [("num_verts", C.c_int), ("num_kps", C.c_int), ("lbs_nnz", C.c_int), ("vpad", C.c_int),
                 ("dirs", _fp), ("j_template", _fp), ("j_shapedirs", _fp), ("parents", _ip),
@@ -305,6 +316,9 @@ SIGNATURES = {
     "hmmr_ief_workspace_bytes": (C.c_size_t, [C.c_int, C.c_int, C.c_int]),
     "hmmr_ief_fwd": (C.c_int, [C.POINTER(IefWeights), _fp, C.c_int, _fp, _vp, C.c_size_t, _vp]),
     "hmmr_ief_fwd_from": (C.c_int, [C.POINTER(IefWeights), _fp, _fp, C.c_int, _fp, _vp, C.c_size_t, _vp]),
+    "hmmr_ief_bwd_workspace_bytes": (C.c_size_t, [C.c_int, C.c_int, C.c_int]),
+    "hmmr_ief_fwd_train": (C.c_int, [C.POINTER(IefWeights), _fp, _fp, _vp, C.c_float, C.c_int, _fp, _vp, C.c_size_t, _vp]),
+    "hmmr_ief_bwd": (C.c_int, [C.POINTER(IefWeights), C.POINTER(IefBwdDesc), _vp, C.c_size_t, _vp]),
     "hmmr_smpl_workspace_bytes": (C.c_size_t, [C.c_int]),
     "hmmr_smpl_fwd": (C.c_int, [C.POINTER(SmplConsts), _fp, C.c_int, _fp, C.c_int, _fp, C.c_int, C.c_int,
                                 _fp, _fp, _fp, _fp, _vp, C.c_size_t, _vp]),

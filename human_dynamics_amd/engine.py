@@ -144,6 +144,9 @@ class HmmrEngine(object):
             self.iw, self.reg_keys = packing.pack_ief(w, self.ief_dtype, self.store, self.delta_keys)
         else:
             self.iw, self.reg_keys = None, [0]
+        # the trainable fp32 bank of the regressors: packed on first use (ief_bank) from these arrays, whatever ief_dtype is
+        self._ief_source = {k: v for k, v in w.items() if k.startswith("single_view_ief") or k == "mean_param"} if self.iw is not None else None
+        self._ief_bank = None
         # an all-fp32 engine is the exact-arithmetic reference (the probe's last rung, the saturation fallback): its SMPL blend product
         # stays on fp32 operands too, so nothing in it can clamp
         all_f32 = (self.dtype, self.temporal_dtype, self.ief_dtype) == (L.HMMR_F32,) * 3
@@ -472,6 +475,77 @@ class HmmrEngine(object):
     def use_optcam(self):
         """True when the packed delta regressors predict 72 values and get the fixed camera [1, 0, 0] (models.py:333-371)."""
         return self.iw is None or not self.iw.no_optcam
+
+    # -- the regressors under training (csrc/ief_grad.hip) ------------------------
+    def ief_bank(self):
+        """The trainable IEF bank (ief_bank.IefBank): an HMMR_F32 pack of the engine's regressors whose layers are tensor views of
+        the packed memory, whatever `ief_dtype` the engine runs.  Packed on the first call: an inference-only process never pays
+        for it.  The inference path (`ief`) keeps its own pack and does not see updates of the bank."""
+        self._need(self.iw, "single_view_ief*/3D_module/* and mean_param")
+        if self._ief_bank is None:
+            from .ief_bank import IefBank
+            self._ief_bank = IefBank(self._ief_source, [k for k in self.reg_keys if k != 0], self.device, num_stages=self.iw.num_stages)
+        return self._ief_bank
+
+    def _ief_train_args(self, strips, omega_start, keep, keep_prob, use_delta_from_pred):
+        bank = self.ief_bank()
+        strips = self.to_device(strips).reshape(-1, 2048)
+        m, R, S = strips.shape[0], bank.iw.num_regressors, bank.iw.num_stages
+        start = None
+        if omega_start is not None:
+            start = self.to_device(omega_start).reshape(-1, 85)
+            if start.shape[0] == 1:
+                start = start.expand(m, 85).contiguous()
+            if start.shape != (m, 85):
+                raise ValueError("omega_start: expected [%d, 85], got %s" % (m, tuple(start.shape)))
+        scale = 1.0
+        if keep is not None:
+            keep = (keep if isinstance(keep, torch.Tensor) else torch.tensor(np.asarray(keep))).to(self.device, torch.uint8).contiguous()
+            if tuple(keep.shape) != (R, S, 2, m, 1024):
+                raise ValueError("keep: expected a uint8 mask of shape %s, got %s" % ((R, S, 2, m, 1024), tuple(keep.shape)))
+            if keep_prob is None or not (0.0 < float(keep_prob) <= 1.0):
+                raise ValueError("keep is given: keep_prob must lie in (0, 1], got %r" % (keep_prob,))
+            scale = 1.0 / float(keep_prob)
+        iw = L.IefWeights.from_buffer_copy(bank.iw)          # a per-call copy of the (host) struct: the shared one is never toggled
+        iw.delta_from_start = int(not use_delta_from_pred)
+        nbytes = self.lib.hmmr_ief_bwd_workspace_bytes(m, R, S)
+        ws = self._ws.setdefault("ief_grad", _Workspace(self.device)).get(nbytes)
+        return bank, iw, strips, start, keep, scale, m, R, ws, nbytes
+
+    def ief_train(self, strips, omega_start=None, keep=None, keep_prob=None, use_delta_from_pred=True):
+        """The training form of `ief` on the fp32 bank (hmmr_ief_fwd_train): strips [m,2048] -> omegas [R,m,85].  keep: uint8
+        [R, num_stages, 2, m, 1024] of zeros and ones (the dropout behind fc1 and fc2 of every stage, src/models.py:103-105) with
+        keep_prob, the probability it was drawn with (the kept units are scaled by 1 / keep_prob); None = no dropout."""
+        bank, iw, strips, start, keep, scale, m, R, ws, nbytes = self._ief_train_args(strips, omega_start, keep, keep_prob, use_delta_from_pred)
+        out = torch.empty((R, m, 85), dtype=torch.float32, device=self.device)
+        L.check(self.lib.hmmr_ief_fwd_train(C.byref(iw), strips.data_ptr(), L.ptr(start), L.ptr(keep), scale, m, out.data_ptr(),
+                                            ws.data_ptr(), nbytes, self._stream()), "hmmr_ief_fwd_train")
+        return out
+
+    def ief_backward(self, strips, d_omegas, omega_start=None, keep=None, keep_prob=None, use_delta_from_pred=True,
+                     want_strips=True, want_start=None, want_weights=True):
+        """The derivative of `ief_train` (hmmr_ief_bwd): the forward's inputs as it took them and d_omegas [R,m,85] ->
+        (d_strips [m,2048] or None, d_omega_start [m,85] or None, [{name: gradient}] per regressor in the bank's layouts).
+        want_weights: True, False, or per regressor a collection of the names wanted (ief_bank.NAMES); what is not wanted is None and
+        its launches are not queued.  want_start defaults to `omega_start is not None`.  Nothing is kept from a forward call."""
+        from .ief_bank import NAMES
+        bank, iw, strips, start, keep, scale, m, R, ws, nbytes = self._ief_train_args(strips, omega_start, keep, keep_prob, use_delta_from_pred)
+        d_omegas = self.to_device(d_omegas).reshape(R, m, 85).contiguous()
+        want_start = (start is not None) if want_start is None else bool(want_start)
+        d = L.IefBwdDesc()
+        d.strips, d.omega_start, d.keep, d.keep_scale, d.m, d.d_omegas = strips.data_ptr(), L.ptr(start), L.ptr(keep), scale, m, d_omegas.data_ptr()
+        d_strips = torch.empty((m, 2048), dtype=torch.float32, device=self.device) if want_strips else None
+        d_start = torch.empty((m, 85), dtype=torch.float32, device=self.device) if want_start else None
+        d.d_strips, d.d_omega_start = L.ptr(d_strips), L.ptr(d_start)
+        grads = []
+        for r in range(R):
+            names = NAMES if want_weights is True else (() if not want_weights else tuple(want_weights[r] or ()))
+            g = {n: (torch.empty(bank.params[r][n].shape, dtype=torch.float32, device=self.device) if n in names else None) for n in NAMES}
+            for n in NAMES:
+                setattr(d.reg[r], "d_" + n, L.ptr(g[n]))
+            grads.append(g)
+        L.check(self.lib.hmmr_ief_bwd(C.byref(iw), C.byref(d), ws.data_ptr(), nbytes, self._stream()), "hmmr_ief_bwd")
+        return d_strips, d_start, grads
 
     def smpl(self, theta, beta, cams=None, want_rs=True):
         """theta [m,72], beta [m,10], cams [m,3] or None (row-major views with a

@@ -82,3 +82,39 @@ def batch_pred_omega(input_features, batch_size, is_training, num_output, omega_
                     use_delta_from_pred=use_delta_from_pred)
     om = om.reshape(om.shape[0], batch_size, sequence_length, 85)
     return om[0], {k: om[i] for i, k in enumerate(engine.reg_keys) if k != 0}
+
+
+def batch_pred_omega_train(input_features, batch_size, is_training, num_output, omega_mean,
+                           sequence_length, scope, engine, predict_delta_keys=(),
+                           use_delta_from_pred=False, use_optcam=False, keep=None, keep_prob=0.5, generator=None,
+                           return_keep=False):
+    """batch_pred_omega under torch.autograd (ief_autograd.ief_apply on the engine's trainable fp32 bank, hmmr_ief_fwd_train /
+    hmmr_ief_bwd): [B,T,2048] -> (omega [B,T,85], {delta_t: [B,T,85]}), differentiable in input_features, omega_mean and the tensors
+    of engine.ief_bank().  is_training=True runs slim.dropout(keep_prob) behind fc1 and fc2 of every stage of every regressor
+    (src/models.py:103-105): the mask is drawn here with torch on the engine's device (`generator`), or given as `keep` (uint8
+    [R, num_stages, 2, B*T, 1024]) to replay a recorded step; return_keep=True returns it as a third value.  The draws are torch's,
+    not TensorFlow's stream, as util/tube_augmentation.py says of its own.  is_training=False: no dropout (keep is ignored)."""
+    import torch
+    from .ief_autograd import ief_apply
+    if num_output != 85:
+        raise ValueError("batch_pred_omega_train: num_output is 85 (3 camera + 72 pose + 10 shape), got %r" % (num_output,))
+    if scope != "single_view_ief":
+        raise ValueError("the engine's regressors were packed from scope 'single_view_ief', got %r" % (scope,))
+    keys = [k for k in sorted(predict_delta_keys) if k != 0]
+    if keys != [k for k in engine.reg_keys if k != 0]:
+        raise ValueError("engine was packed for delta keys %s" % engine.reg_keys)
+    if keys and bool(use_optcam) != engine.use_optcam:
+        raise ValueError("use_optcam=%s, but the checkpoint's delta regressors are %d-wide" %
+                         (use_optcam, 72 if engine.use_optcam else 75))
+    m = batch_size * sequence_length
+    bank = engine.ief_bank()
+    if not is_training:
+        keep = None
+    elif keep is None:
+        shape = (bank.num_regressors, bank.iw.num_stages, 2, m, 1024)
+        keep = (torch.rand(shape, device=engine.device, generator=generator) < keep_prob).to(torch.uint8)
+    om = ief_apply(engine, input_features.reshape(m, -1), omega_start=omega_mean, keep=keep, keep_prob=keep_prob if keep is not None else None,
+                   use_delta_from_pred=use_delta_from_pred)
+    om = om.reshape(om.shape[0], batch_size, sequence_length, 85)
+    out = (om[0], {k: om[i] for i, k in enumerate(engine.reg_keys) if k != 0})
+    return out + (keep,) if return_keep else out

@@ -524,6 +524,60 @@ int hmmr_ief_fwd_from(const hmmr_ief_weights_t* w, const float* strips, const fl
                       void* ws, size_t ws_bytes, void* stream);
 
 /* ------------------------------------------------------------------------- *
+ * IEF backward (additive to ABI 19; csrc/ief_grad.hip): the regressors as the trainer runs them
+ * (src/trainer_sequence_fc.py on precomputed movie strips; slim.dropout(0.5) behind fc1 and fc2, src/models.py:103-105) and
+ * their derivative.  The function differentiated is the exact fp32 one: both entry points take a bank packed with
+ * dtype == HMMR_F32 (plain [cout_pad][K] fp32 rows, fc1_theta [1024][128], biases in `shift`, no `scale`) and refuse every other.
+ * For regressor r and stage s, theta_0 = the regressor's start:
+ *     a1 = phi . W1[:2048] + b1 + theta_s . W1[2048:]      h1 = relu(a1) * keep[r][s][0] * keep_scale
+ *     a2 = h1 . W2 + b2                                    h2 = relu(a2) * keep[r][s][1] * keep_scale
+ *     theta_{s+1} = theta_s + h2 . W3 + b3
+ * keep: uint8 [R][num_stages][2][m][1024] of zeros and ones, or NULL = no dropout (then keep_scale is not read, and the result is
+ * bit for bit that of an all-ones mask with keep_scale = 1); keep_scale = 1 / keep_prob.  relu'(0) = 0.  The regressors are wired
+ * as in hmmr_ief_fwd_from (no_optcam / delta_from_start) and there is no stop-gradient: with use_delta_from_pred a delta's start
+ * omega0[:, 3:75] (or [:, :75]) and the beta columns 75..84 it copies pass their gradient to the present regressor's output, with
+ * delta_from_start to omega_start; columns 0..2 of a 72-wide delta's d_omega belong to the constants [1, 0, 0] and are ignored.
+ * Order of the backward: the delta regressors in regressor order; their contributions to d_omega0 (or d_omega_start) added in
+ * that order; the present regressor; d_strips is added up in the same order.  No floating-point atomics, every contraction in a
+ * fixed order with a split that does not depend on m: equal inputs give equal bytes, a row's d_strips / d_omega_start does not
+ * depend on the other rows of the call, grouped and ungrouped launches (hmmr_debug_t.ief_no_group) give the same bytes.
+ * Nothing is kept from a forward call: hmmr_ief_bwd recomputes it into its workspace by the routine hmmr_ief_fwd_train runs.
+ * ------------------------------------------------------------------------- */
+typedef struct {                       /* one regressor's gradients in the layouts of the HMMR_F32 bank itself; each may be NULL */
+    float* d_fc1_phi;                  /* [1024][2048] */
+    float* d_fc1_theta;                /* [1024][128], columns >= nd written as zeros */
+    float* d_fc2;                      /* [1024][1024] */
+    float* d_fc3;                      /* [128][1024], rows >= nd written as zeros */
+    float* d_b1;                       /* [1024] */
+    float* d_b2;                       /* [1024] */
+    float* d_b3;                       /* [128], entries >= nd written as zeros */
+} hmmr_ief_reg_grads_t;
+
+typedef struct {
+    const float* strips;               /* [m][2048]: the forward's inputs ... */
+    const float* omega_start;          /* [m][85] or NULL = w->mean_theta in every row */
+    const unsigned char* keep;         /* [R][num_stages][2][m][1024] or NULL */
+    float keep_scale;
+    int m;
+    const float* d_omegas;             /* [R][m][85]: the gradient of a loss with respect to what hmmr_ief_fwd_train returned */
+    float* d_strips;                   /* [m][2048] or NULL.  Outputs: a NULL one is skipped and its launches are not queued; at least */
+    float* d_omega_start;              /* [m][85] or NULL      one is required (with omega_start NULL: the gradient of the broadcast rows) */
+    hmmr_ief_reg_grads_t reg[HMMR_MAX_REGRESSORS];
+} hmmr_ief_bwd_desc_t;
+
+/* One layout for both entry points: 0 for m <= 0, num_regressors outside 1..HMMR_MAX_REGRESSORS or num_stages < 1. */
+size_t hmmr_ief_bwd_workspace_bytes(int m, int num_regressors, int num_stages);
+/* The training form of hmmr_ief_fwd_from: omegas [num_regressors][m][85] in the same layout.  Workspace:
+ * hmmr_ief_bwd_workspace_bytes(m, w->num_regressors, w->num_stages).  Refused with -1 before anything is queued: a null w,
+ * strips, omegas or ws; m <= 0; a bank that is not HMMR_F32; bad num_regressors / num_stages / nd; keep given with a
+ * keep_scale that is not a positive finite number; a workspace that is too small. */
+int hmmr_ief_fwd_train(const hmmr_ief_weights_t* w, const float* strips, const float* omega_start, const unsigned char* keep,
+                       float keep_scale, int m, float* omegas, void* ws, size_t ws_bytes, void* stream);
+/* Refused with -1 before anything is queued: what hmmr_ief_fwd_train refuses (desc->strips, ...), a null desc or d_omegas, and a
+ * descriptor that asks for no output. */
+int hmmr_ief_bwd(const hmmr_ief_weights_t* w, const hmmr_ief_bwd_desc_t* desc, void* ws, size_t ws_bytes, void* stream);
+
+/* ------------------------------------------------------------------------- *
  * SMPL forward + keypoint projection: SMPL.__call__ (src/tf_smpl/batch_smpl.py:
  * 89-162), batch_rodrigues / batch_global_rigid_transformation
  * (src/tf_smpl/batch_lbs.py:42-60, 133-194), batch_orth_proj_idrot
