@@ -969,49 +969,152 @@ def b1_unit(h1, conv2, w3_hwio, bias3, pre, w1_hwio, bn1, res=None, shortcut=Non
     pre = (scale, shift) [256], w1 [1,1,256,64], bn1 = (scale, shift) [64]; either res [n,h,w,256] (a float array: the identity
     shortcut) or shortcut = (xp [n,h,w,64], wsc [1,1,64,256], bias [256]) folded into conv3.  Returns the split device tensors
     (trunk [n,h,w,256], h1' [n,h,w,64])."""
-    lib = L.load()
-    dev = torch.device(device)
-    store = packing.DeviceStore(dev)
-    X3 = L.HMMR_F16X3
-    x = h1.contiguous() if isinstance(h1, torch.Tensor) and h1.is_cuda else store.put(np.asarray(h1, np.float32), packing.SPLIT)
-    n, h, w_, cm = x.shape
-    w2 = np.asarray(conv2[0], np.float32)
-    k2 = packing.row_pow2(packing.pack_conv_weight(w2)[:64])
-    w3 = np.asarray(w3_hwio, np.float32)[0, 0]                                   # [K][256]
-    b3 = np.asarray(bias3, np.float64)
-    d = L.TailDesc()
-    if shortcut is not None:
-        xp = store.put(np.asarray(shortcut[0], np.float32), packing.SPLIT)
-        w3 = np.concatenate([w3, np.asarray(shortcut[1], np.float32)[0, 0]], axis=0)
-        b3 = b3 + np.asarray(shortcut[2], np.float64)
-        d.xp, d.c_xp = xp.data_ptr(), 64
-    else:
-        rt = store.put(np.asarray(res, np.float32), packing.SPLIT)
-        d.res, d.ldr = rt.data_ptr(), 256
-    w1 = np.asarray(w1_hwio, np.float32)[0, 0]                                   # [256][64]
-    stream = store.put_tensor(packing.pack_b1_unit_stream(w2, k2, w3.T, w1.T))
-    assert stream.numel() * 2 == lib.hmmr_b1_unit_stream_bytes(0 if shortcut is None else 64)
-    k3, k1 = packing.row_pow2(w3.T), packing.row_pow2(w1.T)
-    out = packing.empty_act((n, h, w_, 256), X3, dev, zero=True)
-    h1n = packing.empty_act((n, h, w_, 64), X3, dev, zero=True)
-    d.dtype, d.m, d.c_mid, d.depth, d.n2 = X3, n * h * w_, cm, 256, 64
-    d.h1, d.hin, d.win, d.ho, d.wo = x.data_ptr(), h, w_, h, w_
-    d.unit_stream = stream.data_ptr()
-    d.scale2 = store.vec((np.asarray(conv2[1], np.float64) * np.exp2(-k2.astype(np.float64))).astype(np.float32)).data_ptr()
-    d.shift2 = store.vec(conv2[2]).data_ptr()
-    d.scale3 = store.vec(np.exp2(-k3.astype(np.float64)).astype(np.float32)).data_ptr()
-    d.shift3 = store.vec(b3.astype(np.float32)).data_ptr()
-    d.pre_scale, d.pre_shift = store.vec(pre[0]).data_ptr(), store.vec(pre[1]).data_ptr()
-    d.scale1 = store.vec((np.asarray(bn1[0], np.float64) * np.exp2(-k1.astype(np.float64))).astype(np.float32)).data_ptr()
-    d.shift1, d.relu1 = store.vec(bn1[1]).data_ptr(), 1
-    d.out, d.out_h1 = out.data_ptr(), h1n.data_ptr()
-    L.check(lib.hmmr_bottleneck_tail(C.byref(d), torch.cuda.current_stream(dev).cuda_stream), "hmmr_bottleneck_tail")
-    torch.cuda.synchronize(dev)
-    return out, h1n
+    c = B1UnitCall(h1, conv2, w3_hwio, bias3, pre, w1_hwio, bn1, res=res, shortcut=shortcut, device=device)
+    c.run()
+    torch.cuda.synchronize(c.dev)
+    n, h, w_ = c.grid
+    return c.trunk.view(n, h, w_, 256), c.h1.view(n, h, w_, 64)
 
 
-PAIR_NAN_WORD = 0x7e007e00          # two fp16 NaNs: what the guard rows / columns of a UnitPairCall's inputs hold
+PAIR_NAN_WORD = 0x7e007e00          # two fp16 NaNs: what the guard rows / columns of a UnitPairCall's / B1UnitCall's inputs hold
 PAIR_SENTINEL = 0x5a5a5a5a          # ... and what its outputs hold before the launch, valid rows included
+
+
+def pack_b1_unit(conv2, w3_hwio, w1_hwio, shortcut=None):
+    """The filter stream of a B1UnitCall (host work: packing.pack_b1_unit_stream of conv2 = (w2 [3,3,64,64], ...), w3 [1,1,64,256] with
+    the folded shortcut's wsc = shortcut[1] appended along K, and w1 [1,1,256,64]) as a host tensor."""
+    w2 = np.asarray(conv2[0], np.float32)
+    w3 = np.asarray(w3_hwio, np.float32)[0, 0]                                   # [K][256]
+    if shortcut is not None:
+        w3 = np.concatenate([w3, np.asarray(shortcut[1], np.float32)[0, 0]], axis=0)
+    k2 = packing.row_pow2(packing.pack_conv_weight(w2)[:64])
+    return packing.pack_b1_unit_stream(w2, k2, w3.T, np.asarray(w1_hwio, np.float32)[0, 0].T)
+
+
+class B1UnitCall(object):
+    """Test/utility entry for the whole-unit kernel of block 1 (hmmr_tail_desc_t.unit_stream, csrc/b1_unit.hip; f16x3) ALONE, and for the
+    three hmmr_conv_gemm launches it replaces on the same device operands: conv2 with k_order = 2 (csrc/conv3x3_stream.hip, tiles 19 /
+    20), conv3 with the shortcut as `res` or as the second K source `in2`, and the fused-preact conv1.
+    h1 [n,h,w,64] (a split device tensor or a float array), conv2 = (w2 [3,3,64,64], scale2, shift2), w3 [1,1,64,256], bias3 [256] or None,
+    pre = (scale, shift) [256], w1 [1,1,256,64], bn1 = (scale, shift) [64]; either res [n,h,w,256] (the identity shortcut) or
+    shortcut = (xp [n,h,w,64], wsc [1,1,64,256], bias [256] or None) folded into conv3.  With neither bias, shift3 = NULL.
+      relu1: ReLU on h1' (else only the clamp to the fp16 range);
+      res_ld > 256: the kernel reads the shortcut out of rows of res_ld elements whose extra columns hold PAIR_NAN_WORD (the three
+        launches always get it contiguous);
+      guard_rows: h1, xp and res are followed by that many rows of NaN halves, trunk and h1' by that many rows of PAIR_SENTINEL -- the
+        valid rows of the outputs start as PAIR_SENTINEL too, not as zeros;
+      stream: the device tensor of pack_b1_unit(...) if the caller has packed it already (host work);
+      three_launches: build the three hmmr_conv_gemm launches instead of the unit kernel (.h2 is their intermediate).
+    .descs are the descriptors run() launches (a test may edit them), .trunk [M + guard_rows, 256] / .h1 [M + guard_rows, 64] the split
+    outputs as rows of pixels, .grid = (n, h, w)."""
+
+    def __init__(self, h1, conv2, w3_hwio, bias3, pre, w1_hwio, bn1, res=None, shortcut=None, relu1=True, res_ld=0, guard_rows=0,
+                 stream=None, three_launches=False, device="cuda:0"):
+        self.lib = L.load()
+        dev = self.dev = torch.device(device)
+        store = self.store = packing.DeviceStore(dev)
+        X3 = L.HMMR_F16X3
+
+        def act(x):
+            if isinstance(x, torch.Tensor) and x.is_cuda and x.dtype == torch.int32:
+                return x.contiguous()
+            return packing.to_split(torch.as_tensor(np.asarray(x), dtype=torch.float32).to(dev))
+
+        def guarded(x, ld=0):                                                    # [n,h,w,c] -> rows of pixels (+ NaN rows / columns)
+            x = x.reshape(-1, x.shape[-1])
+            m_, c = x.shape
+            if not guard_rows and ld <= c:
+                return x
+            buf = torch.full((m_ + guard_rows, max(ld, c)), PAIR_NAN_WORD, dtype=torch.int32, device=dev)
+            buf[:m_, :c] = x
+            return buf
+
+        x = act(h1)
+        n, h, w_, cm = x.shape
+        m = n * h * w_
+        self.grid, self.m, self.guard_rows = (n, h, w_), m, guard_rows
+        x = guarded(x)
+        w2 = np.asarray(conv2[0], np.float32)
+        k2 = packing.row_pow2(packing.pack_conv_weight(w2)[:64])
+        w3 = np.asarray(w3_hwio, np.float32)[0, 0]                               # [K][256]
+        w1 = np.asarray(w1_hwio, np.float32)[0, 0]                               # [256][64]
+        b3 = None if bias3 is None else np.asarray(bias3, np.float64)
+        xp = rt = None
+        if shortcut is not None:
+            assert res is None
+            xp = act(shortcut[0])
+            assert tuple(xp.shape) == (n, h, w_, 64), xp.shape
+            xp = guarded(xp)
+            w3 = np.concatenate([w3, np.asarray(shortcut[1], np.float32)[0, 0]], axis=0)
+            if shortcut[2] is not None:
+                b3 = np.asarray(shortcut[2], np.float64) + (0.0 if b3 is None else b3)
+        else:
+            rt = act(res)
+            assert tuple(rt.shape) == (n, h, w_, 256), rt.shape
+            rt = guarded(rt, 0 if three_launches else res_ld)
+        self.inputs = (x, xp, rt)
+        k3, k1 = packing.row_pow2(w3.T), packing.row_pow2(w1.T)
+        sc2 = store.vec((np.asarray(conv2[1], np.float64) * np.exp2(-k2.astype(np.float64))).astype(np.float32))
+        sc3 = store.vec(np.exp2(-k3.astype(np.float64)).astype(np.float32))
+        sc1 = store.vec((np.asarray(bn1[0], np.float64) * np.exp2(-k1.astype(np.float64))).astype(np.float32))
+        b2, b1 = store.vec(conv2[2]), store.vec(bn1[1])
+        b3 = store.vec(b3.astype(np.float32)) if b3 is not None else None
+        ps, pb = store.vec(pre[0]), store.vec(pre[1])
+        self.trunk = torch.full((m + guard_rows, 256), PAIR_SENTINEL, dtype=torch.int32, device=dev)
+        self.h1 = torch.full((m + guard_rows, 64), PAIR_SENTINEL, dtype=torch.int32, device=dev)
+        ptr = lambda t: t.data_ptr() if t is not None else None
+        if three_launches:
+            self.h2 = torch.full((m + guard_rows, 64), PAIR_SENTINEL, dtype=torch.int32, device=dev)
+            w2s = store.put_tensor(packing.pack_conv3x3_stream(w2, k2))
+            w3p = store.put(packing.scale_rows(w3.T, k3), packing.SPLIT)         # [256][K3] rows, K-contiguous (what hmmr_conv_gemm reads)
+            w1p = store.put(packing.scale_rows(w1.T, k1), packing.SPLIT)
+
+            def desc(in_, w, scale, shift, out, cin, cout, k):
+                d = L.ConvDesc()
+                d.in_, d.w, d.scale, d.shift, d.out = in_.data_ptr(), w.data_ptr(), scale.data_ptr(), ptr(shift), out.data_ptr()
+                d.in_dtype = d.out_dtype = X3
+                d.n_img, d.hin, d.win, d.cin = n, h, w_, cin
+                d.in_img_stride, d.in_row_stride, d.in_px_stride = h * w_ * cin, w_ * cin, cin
+                d.kh = d.kw = k
+                d.sy = d.sx = 1
+                d.py = d.px = k // 2
+                d.ho, d.wo, d.cout, d.ldo = h, w_, cout, cout
+                return d
+
+            c2 = desc(x, w2s, sc2, b2, self.h2, 64, 64, 3)
+            c2.relu, c2.k_order = 1, 2
+            c3 = desc(self.h2, w3p, sc3, b3, self.trunk, 64, 256, 1)
+            if xp is not None:
+                c3.in2, c3.cin2 = xp.data_ptr(), 64
+            else:
+                c3.res, c3.ldr = rt.data_ptr(), 256
+            c1 = desc(self.trunk, w1p, sc1, b1, self.h1, 256, 64, 1)
+            c1.relu, c1.pro_scale, c1.pro_shift = int(bool(relu1)), ps.data_ptr(), pb.data_ptr()
+            self.descs, self._call, self._what = [c2, c3, c1], self.lib.hmmr_conv_gemm, "hmmr_conv_gemm (one of the unit's three launches)"
+        else:
+            if stream is None:
+                stream = packing.pack_b1_unit_stream(w2, k2, w3.T, w1.T)
+            self.stream = stream.to(dev)
+            assert self.stream.numel() * 2 == self.lib.hmmr_b1_unit_stream_bytes(0 if xp is None else 64)
+            d = L.TailDesc()
+            d.dtype, d.m, d.c_mid, d.depth, d.n2 = X3, m, cm, 256, 64
+            d.h1, d.hin, d.win, d.ho, d.wo = x.data_ptr(), h, w_, h, w_
+            d.unit_stream = self.stream.data_ptr()
+            d.scale2, d.shift2, d.scale3, d.shift3 = sc2.data_ptr(), b2.data_ptr(), sc3.data_ptr(), ptr(b3)
+            if xp is not None:
+                d.xp, d.c_xp = xp.data_ptr(), 64
+            else:
+                d.res, d.ldr = rt.data_ptr(), rt.shape[1]
+            d.pre_scale, d.pre_shift = ps.data_ptr(), pb.data_ptr()
+            d.scale1, d.shift1, d.relu1 = sc1.data_ptr(), b1.data_ptr(), int(bool(relu1))
+            d.out, d.out_h1 = self.trunk.data_ptr(), self.h1.data_ptr()
+            self.descs, self._call, self._what = [d], self.lib.hmmr_bottleneck_tail, "hmmr_bottleneck_tail (block-1 unit)"
+
+    def run(self):
+        """launch on the current stream (no synchronisation: tools time this)"""
+        st = torch.cuda.current_stream(self.dev).cuda_stream
+        for d in self.descs:
+            L.check(self._call(C.byref(d), st), self._what)
 
 
 class UnitPairCall(object):

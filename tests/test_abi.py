@@ -159,6 +159,35 @@ def test_conv_desc_validation_of_the_round_2_fields():
     assert lib.hmmr_bottleneck_tail(t, None) != 0 and b"supported shapes" in lib.hmmr_last_error()
 
 
+def test_b1_unit_entry_refuses_with_its_messages():
+    """hmmr_bottleneck_tail with unit_stream set (csrc/b1_unit.hip): every check of hmmr_b1_unit_split, each with its message, on dummy
+    pointers -- the checks run in front of the launch.  That a refused call queues nothing: tests/test_gpu_b1_unit_kernel.py."""
+    import b1_unit_cases as B
+    lib = _lib.load()
+
+    def good(form):
+        t = _lib.TailDesc()
+        t.dtype, t.m, t.c_mid, t.depth, t.n2 = _lib.HMMR_F16X3, 6 * 5 * 7, 64, 256, 64
+        t.h1, t.hin, t.win, t.ho, t.wo, t.unit_stream = 0x1000, 5, 7, 5, 7, 0x2000
+        t.scale2 = t.shift2 = t.scale3 = t.shift3 = t.pre_scale = t.pre_shift = t.scale1 = t.shift1 = 0x3000
+        t.out, t.out_h1, t.relu1 = 0x4000, 0x5000, 1
+        if form == "folded":
+            t.xp, t.c_xp = 0x6000, 64
+        else:
+            t.res, t.ldr = 0x6000, 256
+        return t
+
+    assert len(B.REFUSALS) >= 21 and len({r[0] for r in B.REFUSALS}) == len(B.REFUSALS)
+    for name, form, fields, words in B.REFUSALS:
+        t = good(form)
+        B.apply_refusal(t, fields, 0x7000)
+        rc, msg = lib.hmmr_bottleneck_tail(t, None), lib.hmmr_last_error()
+        assert rc != 0 and words.encode() in msg, (name, rc, msg)
+        assert b"hmmr_bottleneck_tail" in msg
+        with pytest.raises(_lib.HmmrError, match=words):
+            _lib.check(rc, name)
+
+
 def test_fragment_major_packing_layout():
     """packing.pack_frag_major: [n][K] -> [n / 32][K / 16][64 lanes][hi, lo][8]; lane = 32 * (k half) + row, i.e. the 16 bytes a
     lane feeds v_mfma_f32_32x32x16_f16 as its A operand (csrc/bottleneck_split.hip reads them straight from L2); fp16 halves

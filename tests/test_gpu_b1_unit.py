@@ -3,7 +3,8 @@
 * csrc/b1_unit.hip, the whole-unit kernel of block 1 (conv2 + conv3 + add + the next unit's preact + conv1 as one launch), against
   the three hmmr_conv_gemm launches it replaces -- bit for bit, per kernel (both forms: identity shortcut, folded conv shortcut;
   ragged last tile; tiles that straddle images) and through the whole ResNet (slim resnet_v2.bottleneck as invoked at
-  /root/reference/src/models.py:65-75, SURVEY App. A);
+  /root/reference/src/models.py:65-75).  That kernel ALONE (every grid shape, tile counts, known answers, float64 on trunk
+  and h1', run flags, refusals): tests/test_gpu_b1_unit_kernel.py;
 * csrc/unit_pair.hip against the two launches IT replaces on ONE batch with the switch of hmmr_resnet50_fwd forced either way
   (hmmr_debug_t.pair_min_pixels), with the library's launch counters as the proof of which kernel ran.  The unit-pair kernel ALONE
   (ragged row counts, persistent-tile geometries, float64, run flags, refusals): tests/test_gpu_unit_pair.py.
@@ -68,13 +69,10 @@ def test_b1_unit_kernel_equals_its_three_launches(shape, folded, gpu_device):
     assert torch.equal(out, trunk), ("trunk", bad_t, float((packing.from_split(out) - packing.from_split(trunk)).abs().max()))
     assert torch.equal(out_h1, h1n), ("h1'", bad_t, float((packing.from_split(out_h1) - packing.from_split(h1n)).abs().max()))
     # ... and against float64 on the operands as stored (the conv2 -> conv3 -> conv1 chain rounds h2 and the trunk to 22 bits)
-    t64 = packing.from_split(out).double().cpu().numpy()
-    x = packing.from_split(h1).double().cpu().numpy()
-    xp_ = np.pad(x, ((0, 0), (1, 1), (1, 1), (0, 0)))
-    c2 = sum(xp_[:, ky:ky + h, kx:kx + w, :] @ d["w2"][ky, kx].astype(np.float64) for ky in range(3) for kx in range(3))
-    h2r = np.maximum(c2 * d["bn2"][0] + d["bn2"][1], 0)
-    ref = h2r @ d["w3"][0, 0].astype(np.float64) + d["b3"]
-    ref = ref + (d["xp"].astype(np.float64) @ d["wsc"][0, 0].astype(np.float64) + d["bsc"] if folded else d["res"].astype(np.float64))
+    # (the one float64 reference of the unit: tests/b1_unit_cases.py; the kernel alone, trunk AND h1': tests/test_gpu_b1_unit_kernel.py)
+    import b1_unit_cases as B
+    t64 = packing.from_split(out).double().cpu().numpy().reshape(-1, 256)
+    ref = B.reference(d, {k: d[k] for k in ("h1", "xp", "res") if k in d})[1]
     assert np.abs(t64 - ref).max() < 2e-5 * max(1.0, np.abs(ref).max())
 
 
