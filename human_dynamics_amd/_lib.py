@@ -160,6 +160,26 @@ class IefBwdDesc(C.Structure):
                 ("d_strips", _fp), ("d_omega_start", _fp), ("reg", IefRegGrads * MAX_REGRESSORS)]
 
 
+TEMPORAL_GRAD_NAMES = ("gn1_gamma", "gn1_beta", "conv1", "b1", "gn2_gamma", "gn2_beta", "conv2", "b2")
+HALLUCINATOR_GRAD_NAMES = ("fc1", "fc2", "fc3", "b1", "b2", "b3")
+
+
+class TemporalBlockGrads(C.Structure):
+    """hmmr_temporal_block_grads_t: one temporal block's gradients in the layouts of the HMMR_F32 bank (csrc/movie_grad.hip); each may be NULL"""
+    _fields_ = [("d_" + k, _fp) for k in TEMPORAL_GRAD_NAMES]
+
+
+class TemporalBwdDesc(C.Structure):
+    """hmmr_temporal_bwd_desc_t: one call of the temporal encoder's backward"""
+    _fields_ = [("phi", _fp), ("b", C.c_int), ("t", C.c_int), ("d_strips", _fp), ("d_phi", _fp),
+                ("block", TemporalBlockGrads * MAX_TEMPORAL_BLOCKS)]
+
+
+class HallucinatorBwdDesc(C.Structure):
+    """hmmr_hallucinator_bwd_desc_t: one call of the hallucinator's backward"""
+    _fields_ = [("phi", _fp), ("m", C.c_int), ("d_out", _fp), ("d_phi", _fp)] + [("d_" + k, _fp) for k in HALLUCINATOR_GRAD_NAMES]
+
+
 class SmplConsts(C.Structure):
     _fields_ = [("num_verts", C.c_int), ("num_kps", C.c_int), ("lbs_nnz", C.c_int), ("vpad", C.c_int),
                 ("dirs", _fp), ("j_template", _fp), ("j_shapedirs", _fp), ("parents", _ip),
@@ -319,6 +339,10 @@ SIGNATURES = {
     "hmmr_ief_bwd_workspace_bytes": (C.c_size_t, [C.c_int, C.c_int, C.c_int]),
     "hmmr_ief_fwd_train": (C.c_int, [C.POINTER(IefWeights), _fp, _fp, _vp, C.c_float, C.c_int, _fp, _vp, C.c_size_t, _vp]),
     "hmmr_ief_bwd": (C.c_int, [C.POINTER(IefWeights), C.POINTER(IefBwdDesc), _vp, C.c_size_t, _vp]),
+    "hmmr_temporal_bwd_workspace_bytes": (C.c_size_t, [C.c_int, C.c_int, C.c_int]),
+    "hmmr_temporal_bwd": (C.c_int, [C.POINTER(TemporalWeights), C.POINTER(TemporalBwdDesc), _vp, C.c_size_t, _vp]),
+    "hmmr_hallucinator_bwd_workspace_bytes": (C.c_size_t, [C.c_int]),
+    "hmmr_hallucinator_bwd": (C.c_int, [C.POINTER(HallucinatorWeights), C.POINTER(HallucinatorBwdDesc), _vp, C.c_size_t, _vp]),
     "hmmr_smpl_workspace_bytes": (C.c_size_t, [C.c_int]),
     "hmmr_smpl_fwd": (C.c_int, [C.POINTER(SmplConsts), _fp, C.c_int, _fp, C.c_int, _fp, C.c_int, C.c_int,
                                 _fp, _fp, _fp, _fp, _vp, C.c_size_t, _vp]),

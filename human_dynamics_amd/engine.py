@@ -147,6 +147,9 @@ class HmmrEngine(object):
         # the trainable fp32 bank of the regressors: packed on first use (ief_bank) from these arrays, whatever ief_dtype is
         self._ief_source = {k: v for k, v in w.items() if k.startswith("single_view_ief") or k == "mean_param"} if self.iw is not None else None
         self._ief_bank = None
+        # ... and that of f_movie (the temporal blocks and the hallucinator): movie_bank, the same way
+        self._movie_source = {k: v for k, v in w.items() if k.startswith(("AZ_FC_block", "fc2_res/"))} if self.tw is not None else None
+        self._movie_bank = None
         # an all-fp32 engine is the exact-arithmetic reference (the probe's last rung, the saturation fallback): its SMPL blend product
         # stays on fp32 operands too, so nothing in it can clamp
         all_f32 = (self.dtype, self.temporal_dtype, self.ief_dtype) == (L.HMMR_F32,) * 3
@@ -546,6 +549,104 @@ class HmmrEngine(object):
             grads.append(g)
         L.check(self.lib.hmmr_ief_bwd(C.byref(iw), C.byref(d), ws.data_ptr(), nbytes, self._stream()), "hmmr_ief_bwd")
         return d_strips, d_start, grads
+
+    # -- f_movie under training (csrc/movie_grad.hip) ------------------------------
+    def movie_bank(self):
+        """The trainable f_movie bank (movie_bank.MovieBank): an HMMR_F32 pack of the engine's temporal blocks and, when the checkpoint
+        has one, of the hallucinator, whose layers are tensor views of the packed memory, whatever `temporal_dtype` the engine runs.
+        Packed on the first call: an inference-only process never pays for it.  The inference path (`temporal`, `hallucinate`) keeps
+        its own pack and does not see updates of the bank."""
+        self._need(self.tw, "AZ_FC_block*")
+        if self._movie_bank is None:
+            from .movie_bank import MovieBank
+            self._movie_bank = MovieBank(self._movie_source, self.device, num_conv_layers=self.num_conv_layers)
+        return self._movie_bank
+
+    def _hal_bank(self):
+        bank = self.movie_bank()
+        if bank.hw is None:
+            raise L.HmmrError("the loaded weights have no fc2_res/* variables (pred_mode 'hal')")
+        return bank
+
+    def _movie_ws(self, nbytes):
+        return self._ws.setdefault("movie_grad", _Workspace(self.device)).get(nbytes)
+
+    def temporal_train(self, phi):
+        """`temporal` on the fp32 bank (hmmr_temporal_fwd; the encoder has no dropout, src/models.py:121-228): phi [b,t,2048] ->
+        movie strips [b,t,2048]"""
+        bank = self.movie_bank()
+        phi = self.to_device(phi)
+        b, t, c = phi.shape
+        assert c == 2048
+        out = torch.empty((b, t, c), dtype=torch.float32, device=self.device)
+        nbytes = self.lib.hmmr_temporal_workspace_bytes(b, t, L.HMMR_F32)
+        ws = self._movie_ws(nbytes)
+        L.check(self.lib.hmmr_temporal_fwd(C.byref(bank.tw), phi.data_ptr(), b, t, out.data_ptr(), ws.data_ptr(), nbytes, self._stream()),
+                "hmmr_temporal_fwd")
+        return out
+
+    def hallucinate_train(self, phi):
+        """`hallucinate` on the fp32 bank (hmmr_hallucinator_fwd): phi [..., 2048] -> hallucinated movie strips, same shape"""
+        bank = self._hal_bank()
+        phi = self.to_device(phi)
+        flat = phi.reshape(-1, 2048)
+        m = flat.shape[0]
+        out = torch.empty((m, 2048), dtype=torch.float32, device=self.device)
+        nbytes = self.lib.hmmr_hallucinator_workspace_bytes(m, L.HMMR_F32)
+        ws = self._movie_ws(nbytes)
+        L.check(self.lib.hmmr_hallucinator_fwd(C.byref(bank.hw), flat.data_ptr(), m, out.data_ptr(), ws.data_ptr(), nbytes, self._stream()),
+                "hmmr_hallucinator_fwd")
+        return out.reshape(phi.shape)
+
+    def temporal_backward(self, phi, d_strips, want_phi=True, want_weights=True):
+        """The derivative of `temporal_train` (hmmr_temporal_bwd): phi [b,t,2048] as the forward took it and d_strips [b,t,2048] ->
+        (d_phi [b,t,2048] or None, [{name: gradient}] per block in the bank's layouts).  want_weights: True, False, or per block a
+        collection of the names wanted (movie_bank.BLOCK_NAMES); what is not wanted is None and its launches are not queued.
+        Nothing is kept from a forward call."""
+        from .movie_bank import BLOCK_NAMES
+        bank = self.movie_bank()
+        phi = self.to_device(phi)
+        b, t, c = phi.shape
+        assert c == 2048
+        d_strips = self.to_device(d_strips).reshape(b, t, c)
+        d = L.TemporalBwdDesc()
+        d.phi, d.b, d.t, d.d_strips = phi.data_ptr(), b, t, d_strips.data_ptr()
+        d_phi = torch.empty((b, t, c), dtype=torch.float32, device=self.device) if want_phi else None
+        d.d_phi = L.ptr(d_phi)
+        grads = []
+        for i in range(bank.num_blocks):
+            names = BLOCK_NAMES if want_weights is True else (() if not want_weights else tuple(want_weights[i] or ()))
+            g = {n: (torch.empty(bank.blocks[i][n].shape, dtype=torch.float32, device=self.device) if n in names else None) for n in BLOCK_NAMES}
+            for n in BLOCK_NAMES:
+                setattr(d.block[i], "d_" + n, L.ptr(g[n]))
+            grads.append(g)
+        nbytes = self.lib.hmmr_temporal_bwd_workspace_bytes(b, t, bank.num_blocks)
+        ws = self._movie_ws(nbytes)
+        L.check(self.lib.hmmr_temporal_bwd(C.byref(bank.tw), C.byref(d), ws.data_ptr(), nbytes, self._stream()), "hmmr_temporal_bwd")
+        return d_phi, grads
+
+    def hallucinate_backward(self, phi, d_out, want_phi=True, want_weights=True):
+        """The derivative of `hallucinate_train` (hmmr_hallucinator_bwd): phi [..., 2048] and d_out of the same shape ->
+        (d_phi of that shape or None, {name: gradient} in the bank's layouts).  want_weights: True, False or a collection of the names
+        wanted (movie_bank.HAL_NAMES)."""
+        from .movie_bank import HAL_NAMES
+        bank = self._hal_bank()
+        phi = self.to_device(phi)
+        flat = phi.reshape(-1, 2048)
+        m = flat.shape[0]
+        d_out = self.to_device(d_out).reshape(m, 2048)
+        names = HAL_NAMES if want_weights is True else (() if not want_weights else tuple(want_weights))
+        d = L.HallucinatorBwdDesc()
+        d.phi, d.m, d.d_out = flat.data_ptr(), m, d_out.data_ptr()
+        d_phi = torch.empty((m, 2048), dtype=torch.float32, device=self.device) if want_phi else None
+        d.d_phi = L.ptr(d_phi)
+        g = {n: (torch.empty(bank.hal[n].shape, dtype=torch.float32, device=self.device) if n in names else None) for n in HAL_NAMES}
+        for n in HAL_NAMES:
+            setattr(d, "d_" + n, L.ptr(g[n]))
+        nbytes = self.lib.hmmr_hallucinator_bwd_workspace_bytes(m)
+        ws = self._movie_ws(nbytes)
+        L.check(self.lib.hmmr_hallucinator_bwd(C.byref(bank.hw), C.byref(d), ws.data_ptr(), nbytes, self._stream()), "hmmr_hallucinator_bwd")
+        return (d_phi.reshape(phi.shape) if d_phi is not None else None), g
 
     def smpl(self, theta, beta, cams=None, want_rs=True):
         """theta [m,72], beta [m,10], cams [m,3] or None (row-major views with a

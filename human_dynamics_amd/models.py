@@ -57,6 +57,26 @@ def fc2_res(phi, engine, name="fc2_res"):
     return engine.hallucinate(phi)
 
 
+def az_fc2_groupnorm_train(is_training, net, num_conv_layers, engine):
+    """az_fc2_groupnorm under torch.autograd (movie_autograd.temporal_apply on the engine's trainable fp32 bank, hmmr_temporal_fwd /
+    hmmr_temporal_bwd): net [B,T,2048] -> movie strips [B,T,2048], differentiable in net and the temporal tensors of
+    engine.movie_bank().  The encoder has no dropout and its GroupNorm no moving statistics (src/models.py:121-228), so is_training
+    selects nothing: both values run the same function."""
+    from .movie_autograd import temporal_apply
+    if num_conv_layers != engine.num_conv_layers:
+        raise ValueError("engine was packed with num_conv_layers=%d" % engine.num_conv_layers)
+    return temporal_apply(engine, net)
+
+
+def fc2_res_train(phi, engine, name="fc2_res"):
+    """fc2_res under torch.autograd (movie_autograd.hallucinate_apply): phi [B,T,2048] -> hallucinated movie strip [B,T,2048],
+    differentiable in phi and the hallucinator's tensors of engine.movie_bank()  (src/models.py:270-296)."""
+    from .movie_autograd import hallucinate_apply
+    if name != "fc2_res":
+        raise ValueError("the engine's hallucinator was packed from scope 'fc2_res', got %r" % (name,))
+    return hallucinate_apply(engine, phi)
+
+
 def batch_pred_omega(input_features, batch_size, is_training, num_output, omega_mean,
                      sequence_length, scope, engine, predict_delta_keys=(),
                      use_delta_from_pred=False, use_optcam=False):

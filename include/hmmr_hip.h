@@ -578,6 +578,66 @@ int hmmr_ief_fwd_train(const hmmr_ief_weights_t* w, const float* strips, const f
 int hmmr_ief_bwd(const hmmr_ief_weights_t* w, const hmmr_ief_bwd_desc_t* desc, void* ws, size_t ws_bytes, void* stream);
 
 /* ------------------------------------------------------------------------- *
+ * f_movie / hallucinator backward (additive to ABI 19; csrc/movie_grad.hip): the derivative of the two modules the
+ * reference's sequence trainer trains in front of the regressors (src/trainer_sequence_fc.py:635-665, 839-846).  Neither has a
+ * dropout (src/models.py:121-228, 270-296), so the training forward IS hmmr_temporal_fwd / hmmr_hallucinator_fwd on a bank packed
+ * with dtype == HMMR_F32: conv*.w plain [2048][3*2048] fp32 rows with k = tap*2048 + ci (fc*.w [2048][2048]), the bias in `shift`,
+ * no `scale`.  The function differentiated is that exact fp32 one; every other dtype is refused.  Per temporal block, on the rows
+ * of one window (rows outside it are zeros):
+ *     h1 = relu(GN1(x))    c1[r] = b1 + sum_tap h1[r + tap - 1] . W1[:, tap]    h2 = relu(GN2(c1))    y = x + b2 + conv(h2, W2)
+ * GN: 32 groups, mean and population variance over (t, 64 channels), eps 1e-6, recomputed in the forward's two-pass form.
+ * Hallucinator: h1 = relu(phi . W1^T + b1), h2 = relu(h1 . W2^T + b2), out = phi + h2 . W3^T + b3.
+ * Contract:
+ *  - Nothing is kept from a forward call.  The backward recomputes the forward into its workspace with the launches
+ *    hmmr_temporal_fwd / hmmr_hallucinator_fwd queue on an fp32 bank (hmmr_groupnorm_relu, then hmmr_conv_gemm with the same
+ *    split-K); the last layer's output, which no gradient reads, is not recomputed.  Per block it keeps the block input, the
+ *    conv1 output and the two GN+ReLU outputs, all fp32.
+ *  - The ReLU gate is h > 0 on the stored GN+ReLU (fc+ReLU) output: relu'(0) = 0.
+ *  - No floating-point atomics; every contraction and reduction has a fixed order: equal inputs give equal bytes.
+ *  - The data-gradient contraction (6144 long for a conv, 2048 for an fc) is cut into 8 fixed slices added in slice order; the
+ *    split does not depend on b, t or m, so a window's d_phi (a row's, for the hallucinator) does not depend on the other windows
+ *    (rows) of the call.  The weight gradients contract over the b*t (m) rows in 4 slices; d_gamma / d_beta / bias gradients are
+ *    summed in window (row) order in double and rounded once.
+ *  - A NULL output is skipped and its launches are not queued; with d_phi NULL the chain stops at the lowest block that has a
+ *    wanted gradient.
+ *  - Refused with -1 before anything is queued: a null w, desc, phi, cotangent or ws; non-positive b, t or m; a bank that is not
+ *    HMMR_F32 (or has a scaled / missing layer); num_blocks outside 1..HMMR_MAX_TEMPORAL_BLOCKS; a descriptor that asks for no
+ *    output (gradients of blocks >= num_blocks do not count); a workspace that is too small.
+ * ------------------------------------------------------------------------- */
+typedef struct {                       /* one block's gradients in the layouts of the HMMR_F32 bank itself; each may be NULL */
+    float* d_gn1_gamma; float* d_gn1_beta;     /* [2048] */
+    float* d_conv1; float* d_b1;               /* [2048][6144], [2048] */
+    float* d_gn2_gamma; float* d_gn2_beta;
+    float* d_conv2; float* d_b2;
+} hmmr_temporal_block_grads_t;
+
+typedef struct {
+    const float* phi;                  /* [b][t][2048]: the forward's input */
+    int b, t;
+    const float* d_strips;             /* [b][t][2048]: the gradient of a loss with respect to what hmmr_temporal_fwd returned */
+    float* d_phi;                      /* [b][t][2048] or NULL */
+    hmmr_temporal_block_grads_t block[HMMR_MAX_TEMPORAL_BLOCKS];
+} hmmr_temporal_bwd_desc_t;
+
+/* 0 for b <= 0, t <= 0 or num_blocks outside 1..HMMR_MAX_TEMPORAL_BLOCKS. */
+size_t hmmr_temporal_bwd_workspace_bytes(int b, int t, int num_blocks);
+int hmmr_temporal_bwd(const hmmr_temporal_weights_t* w, const hmmr_temporal_bwd_desc_t* desc, void* ws, size_t ws_bytes, void* stream);
+
+typedef struct {
+    const float* phi;                  /* [m][2048]: the forward's input */
+    int m;
+    const float* d_out;                /* [m][2048] */
+    float* d_phi;                      /* [m][2048] or NULL */
+    float* d_fc1; float* d_fc2; float* d_fc3;  /* [2048][2048] each, or NULL */
+    float* d_b1; float* d_b2; float* d_b3;     /* [2048] each, or NULL */
+} hmmr_hallucinator_bwd_desc_t;
+
+/* 0 for m <= 0. */
+size_t hmmr_hallucinator_bwd_workspace_bytes(int m);
+int hmmr_hallucinator_bwd(const hmmr_hallucinator_weights_t* w, const hmmr_hallucinator_bwd_desc_t* desc, void* ws, size_t ws_bytes,
+                          void* stream);
+
+/* ------------------------------------------------------------------------- *
  * SMPL forward + keypoint projection: SMPL.__call__ (src/tf_smpl/batch_smpl.py:
  * 89-162), batch_rodrigues / batch_global_rigid_transformation
  * (src/tf_smpl/batch_lbs.py:42-60, 133-194), batch_orth_proj_idrot
