@@ -12,12 +12,8 @@
 // struct's dtype.  All GEMMs go through the implicit-GEMM kernel.
 #include "common.h"
 #include "hmmr_hip.h"
+#include "tail_sched.h"      // LDT, IEF_SPLIT_K, fc_desc, ief_finalize_kernel
 #include "workspace.h"
-
-static constexpr int LDT = 128;      // row stride of the zero-padded theta state
-// The K = 2048 / 1024 GEMMs have at most m/64 x 16 output tiles (m = kept frames of a step, a few
-// hundred): 4 K-slices fill the chip.  Fixed per layer so a row's result is batch-independent.
-static constexpr int IEF_SPLIT_K = 4;
 
 template <typename TO>
 __global__ void cast_rows_kernel(const float* __restrict__ in, TO* __restrict__ out, long long n8) {
@@ -46,6 +42,7 @@ __global__ void ief_init_theta_kernel(const float* __restrict__ src, int ld_src,
 // mode 2 (delta, no optcam)    -> [theta[:, :75], beta]              (models.py:372-373)
 // beta = columns 75..84 of the delta's starting omega: row `row` of `bsrc` (ld_b = 85) or one broadcast row (ld_b = 0).
 // Grid y = problem of a grouped launch: its theta `th_stride` floats, its output m * 85 floats behind the previous one's.
+// (declared in csrc/tail_sched.h: csrc/ief_grad.hip launches it too)
 __global__ void ief_finalize_kernel(const float* __restrict__ theta, const float* __restrict__ bsrc, int ld_b,
                                     int mode, float* __restrict__ out, int m, long long th_stride) {
     const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
@@ -86,19 +83,6 @@ static IefBufs ief_layout(int m, int dtype, int group) {
 
 extern "C" size_t hmmr_ief_workspace_bytes(int m, int num_regressors, int dtype) {
     return m > 0 ? ief_layout(m, dtype, num_regressors - 1).total : 0;
-}
-
-static hmmr_conv_desc_t fc_desc(const void* in, int in_dtype, int m, int k, const hmmr_layer_t& l,
-                                void* out, int out_dtype, int cout, int ldo, void* sk = nullptr,
-                                size_t skbytes = 0) {
-    hmmr_conv_desc_t d = {};
-    d.in = in; d.w = l.w; d.scale = l.scale; d.shift = l.shift; d.out = out;
-    d.in_dtype = in_dtype; d.out_dtype = out_dtype;
-    d.n_img = m; d.hin = d.win = 1; d.cin = k;
-    d.in_img_stride = k; d.in_row_stride = k; d.in_px_stride = k;
-    d.kh = d.kw = 1; d.sy = d.sx = 1; d.ho = d.wo = 1; d.cout = cout; d.ldo = ldo;
-    if (sk) { d.split_k = IEF_SPLIT_K; d.ws = sk; d.ws_bytes = skbytes; }
-    return d;
 }
 
 extern "C" int hmmr_ief_fwd(const hmmr_ief_weights_t* w, const float* strips, int m, float* omegas,
@@ -182,7 +166,7 @@ extern "C" int hmmr_ief_fwd_from(const hmmr_ief_weights_t* w, const float* strip
                                th[0], th[1], m, ths);
         HMMR_CHECK_HIP(hipGetLastError());
         // pre = phi . W1[:2048] + b1
-        hmmr_conv_desc_t d = fc_desc(xin, w->dtype, m, 2048, R.fc1_phi, pre, w->dtype, 1024, 1024, base + L.sk, L.skbytes);
+        hmmr_conv_desc_t d = fc_desc(xin, w->dtype, m, 2048, R.fc1_phi, pre, w->dtype, 1024, 1024, IEF_SPLIT_K, base + L.sk, L.skbytes);
         group(d, z_phi, 0, (long long)L.pre_s, 0);
         if (hmmr_conv_gemm(&d, s)) return -2;
         int cur = 0;
@@ -193,12 +177,12 @@ extern "C" int hmmr_ief_fwd_from(const hmmr_ief_weights_t* w, const float* strip
             group(d, z_th, (long long)L.th_s, (long long)L.pre_s, (long long)L.pre_s);
             if (hmmr_conv_gemm(&d, s)) return -2;
             // h2 = relu(h1 . W2 + b2)
-            d = fc_desc(h1, w->dtype, m, 1024, R.fc2, h2, w->dtype, 1024, 1024, base + L.sk, L.skbytes);
+            d = fc_desc(h1, w->dtype, m, 1024, R.fc2, h2, w->dtype, 1024, 1024, IEF_SPLIT_K, base + L.sk, L.skbytes);
             d.relu = 1;
             group(d, z_fc2, (long long)L.pre_s, (long long)L.pre_s, 0);
             if (hmmr_conv_gemm(&d, s)) return -2;
             // theta' = theta + h2 . W3 + b3
-            d = fc_desc(h2, w->dtype, m, 1024, R.fc3, th[cur ^ 1], HMMR_F32, R.nd, LDT, base + L.sk, L.skbytes);
+            d = fc_desc(h2, w->dtype, m, 1024, R.fc3, th[cur ^ 1], HMMR_F32, R.nd, LDT, IEF_SPLIT_K, base + L.sk, L.skbytes);
             d.res = th[cur]; d.ldr = LDT;
             group(d, z_fc3, (long long)L.pre_s, (long long)L.th_s, (long long)L.th_s);
             if (hmmr_conv_gemm(&d, s)) return -2;

@@ -9,19 +9,18 @@
 // hmmr_ief_fwd_train runs.  The masked h1 / h2 carry the gate of the backward: h > 0 exactly where a > 0 and keep = 1 (keep_scale > 0),
 // so d_a = d_h * (h > 0 ? keep_scale : 0), and relu'(0) = 0.
 //
-// Two contractions on v_mfma_f32_32x32x2_f32 (one kernel, ief_mm_kernel): the data gradient dX = dY . W sums over the ROWS of the bank as
-// it lies in memory -- with one fp32 value per lane the B operand B[k][j] IS W[k][j0 + lane], a coalesced read of the untransposed bank,
-// no copy and no transposing stage -- and the weight gradient dW = d_a^T . x sums over the rows of the batch, the stages of a regressor
-// laid end to end ([num_stages * m][...]): one launch per layer.  Every output tile is one workgroup whose waves each take a fixed slice
-// of the contraction; the partial tiles are added in slice order.  No atomics; a data-gradient row does not depend on m.
+// Two contractions through csrc/grad_mm.h's kernel, unwindowed, one accumulator set: the data gradient dX = dY . W sums over the ROWS of
+// the bank as it lies in memory, and the weight gradient dW = d_a^T . x sums over the rows of the batch, the stages of a regressor laid
+// end to end ([num_stages * m][...]): one launch per layer.  A data-gradient row does not depend on m.  The recomputed forward is built
+// from csrc/tail_sched.h, as csrc/ief.hip's is.
 #include "common.h"
+#include "grad_mm.h"
 #include "hmmr_hip.h"
+#include "tail_sched.h"
 #include "workspace.h"
 
 #include <math.h>
 
-static constexpr int LDT = 128;          // row stride of the zero-padded theta state (csrc/ief.hip)
-static constexpr int IEF_SPLIT_K = 4;    // the K = 2048 / 1024 GEMMs of the recomputed forward: csrc/ief.hip's split
 static constexpr int G = HMMR_MAX_REGRESSORS;
 
 // ---------------------------------------------------------------------------------------------------------------- small kernels
@@ -35,24 +34,6 @@ __global__ void ief_train_init_theta_kernel(const float* __restrict__ src, int l
     const long long e = i % n;
     const int row = (int)(e / LDT), col = (int)(e % LDT);
     theta[(long long)blockIdx.y * set_stride + i] = (i < n && col < nd) ? src[(long long)row * ld_src + off + col] : 0.f;
-}
-
-// omega_out[m, 85] from the last theta: the three modes of csrc/ief.hip's ief_finalize_kernel
-__global__ void ief_train_finalize_kernel(const float* __restrict__ theta, const float* __restrict__ bsrc, int ld_b, int mode,
-                                          float* __restrict__ out, int m, long long set_stride) {
-    const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= (long long)m * 85) return;
-    const int row = (int)(i / 85), col = (int)(i % 85);
-    theta += (long long)blockIdx.y * set_stride;
-    out += (long long)blockIdx.y * m * 85;
-    float v;
-    if (mode == 0) v = theta[(long long)row * LDT + col];
-    else if (col >= 75) v = bsrc[(long long)row * ld_b + col];
-    else if (mode == 2) v = theta[(long long)row * LDT + col];
-    else if (col == 0) v = 1.f;
-    else if (col < 3) v = 0.f;
-    else v = theta[(long long)row * LDT + (col - 3)];
-    out[i] = v;
 }
 
 // h *= keep * keep_scale, in place on relu(a): n = m * 1024 values.  Grid y = problem: h `set_stride` floats, keep `keep_stride` bytes on.
@@ -108,154 +89,11 @@ __global__ void ief_stage_sum_kernel(const float* __restrict__ x, int stages, lo
     out[(long long)blockIdx.y * set_stride + i] = v;
 }
 
-struct CsPtrs { const float* a[G]; float* out[G]; };
-// out[col] = sum over the K rows of a[K][lda], accumulated in double and rounded once: a plain fp32 chain over the num_stages * m rows
-// loses log2(K) bits that a blocked sum (what the yardstick's fp32 autograd does) keeps -- 7 x E32 on d_b3 at K = 480.  A workgroup owns 32
-// columns; thread (g, c) adds rows g, g + 8, g + 16, ... of column c in row order, and thread (0, c) adds the eight partial sums in g order:
-// a fixed order for a given K.  Grid y = problem; a NULL output is skipped.
-__global__ __launch_bounds__(256) void ief_colsum_kernel(CsPtrs p, int K, int N, int lda) {
-    __shared__ double part[8][32];
-    float* out = p.out[blockIdx.y];
-    if (!out) return;                                   // (the whole workgroup)
-    const int c = threadIdx.x & 31, g = threadIdx.x >> 5;
-    const int col = blockIdx.x * 32 + c;
-    double v = 0.0;
-    if (col < N) {
-        const float* a = p.a[blockIdx.y] + col;
-        for (int k = g; k < K; k += 8) v += (double)a[(long long)k * lda];
-    }
-    part[g][c] = v;
-    __syncthreads();
-    if (g || col >= N) return;
-    for (int q = 1; q < 8; ++q) v += part[q][c];
-    out[col] = (float)v;
-}
-
 // ---------------------------------------------------------------------------------------------------------------- the contraction
-struct MmPtrs { const float* a[G]; const float* b[G]; float* c[G]; const float* res[G]; const float* gate[G]; };
-
-// C[M][N] = sum_k A(i, k) * B[k][j]  with  A(i, k) = A_T ? a[k][i] : a[i][k]   (+ res[i][j]; then * (gate[i][j] > 0 ? gate_scale : 0)).
-// Workgroup = one (32 MI) x (32 NI) tile of C, wave w = slice w of the contraction (ks values each, a multiple of 16); the partial tiles
-// are added in slice order, (((w0 + w1) + w2) + ...).  v_mfma_f32_32x32x2_f32: lane l holds A[i = l & 31][k = l >> 5] and
-// B[k = l >> 5][j = l & 31]; result register q of lane l is C[(q & 3) + 8 (q >> 2) + 4 (l >> 5)][l & 31].  The two values an MFMA takes
-// need not be neighbours: step t of a chunk of 16 takes k0 + t (lanes 0..31) and k0 + 8 + t (lanes 32..63), so that with a row-major A
-// (A_T false, K a multiple of 16) a lane reads its eight values as two 16-byte pieces.  Eight steps of operands are loaded while the
-// MFMAs of the eight before them run (two register sets).  Every read is guarded by the operand's own extent; a
-// guarded-out value is a zero operand.  Grid z = problem of a grouped launch (pointer tables); a problem whose c is NULL is skipped.
-template <bool A_T, int MI, int NI, int SLICES>
-__global__ __launch_bounds__(64 * SLICES) void ief_mm_kernel(MmPtrs p, int M, int N, int K, int lda, int ldb, int ldc, int ldg,
-                                                             float gate_scale) {
-    static_assert((SLICES - 1) * MI * NI * 16 * 64 * 4 <= 64 * 1024, "the partial tiles must fit the static LDS limit");
-    __shared__ float red[SLICES - 1][MI * NI][16][64];
-    float* __restrict__ c = p.c[blockIdx.z];
-    if (!c) return;                                     // (the whole workgroup: blockIdx is uniform)
-    const float* __restrict__ a = p.a[blockIdx.z];
-    const float* __restrict__ b = p.b[blockIdx.z];
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const int r = lane & 31, h = lane >> 5;
-    const int i0 = blockIdx.y * (32 * MI) + r, j0 = blockIdx.x * (32 * NI) + r;
-    const int ks = ((K + SLICES - 1) / SLICES + 15) & ~15;
-    const int kb = wave * ks, ke = min(K, kb + ks);
-    f32x16 acc[MI][NI];
-#pragma unroll
-    for (int mi = 0; mi < MI; ++mi)
-#pragma unroll
-        for (int ni = 0; ni < NI; ++ni)
-#pragma unroll
-            for (int q = 0; q < 16; ++q) acc[mi][ni][q] = 0.f;
-    float a0[8][MI], b0[8][NI], a1[8][MI], b1[8][NI];
-    auto load = [&](float (&av)[8][MI], float (&bv)[8][NI], int k0) {
-        if (!A_T) {                                     // a lane's eight values are consecutive in its row: two 16-byte reads (K % 16 == 0)
-#pragma unroll
-            for (int mi = 0; mi < MI; ++mi) {
-                const int i = i0 + 32 * mi;
-                f32x4 lo = {0.f, 0.f, 0.f, 0.f}, hi = lo;
-                if (k0 < ke && i < M) {
-                    const f32x4* q = (const f32x4*)(a + (long long)i * lda + k0 + 8 * h);
-                    lo = q[0]; hi = q[1];
-                }
-#pragma unroll
-                for (int t = 0; t < 4; ++t) { av[t][mi] = lo[t]; av[4 + t][mi] = hi[t]; }
-            }
-        }
-#pragma unroll
-        for (int t = 0; t < 8; ++t) {
-            const int k = k0 + 8 * h + t;
-            const bool kok = k < ke;
-            if (A_T) {
-#pragma unroll
-                for (int mi = 0; mi < MI; ++mi) {
-                    const int i = i0 + 32 * mi;
-                    av[t][mi] = (kok && i < M) ? a[(long long)k * lda + i] : 0.f;
-                }
-            }
-#pragma unroll
-            for (int ni = 0; ni < NI; ++ni) {
-                const int j = j0 + 32 * ni;
-                bv[t][ni] = (kok && j < N) ? b[(long long)k * ldb + j] : 0.f;
-            }
-        }
-    };
-    auto mma = [&](const float (&av)[8][MI], const float (&bv)[8][NI]) {
-#pragma unroll
-        for (int t = 0; t < 8; ++t)
-#pragma unroll
-            for (int mi = 0; mi < MI; ++mi)
-#pragma unroll
-                for (int ni = 0; ni < NI; ++ni) acc[mi][ni] = __builtin_amdgcn_mfma_f32_32x32x2f32(av[t][mi], bv[t][ni], acc[mi][ni], 0, 0, 0);
-    };
-    load(a0, b0, kb);
-    for (int k0 = kb; k0 < ke; k0 += 32) {                  // (kb, ke and every branch below are the same for a whole wave)
-        if (k0 + 16 < ke) load(a1, b1, k0 + 16);
-        mma(a0, b0);
-        if (k0 + 16 < ke) {
-            if (k0 + 32 < ke) load(a0, b0, k0 + 32);
-            mma(a1, b1);
-        }
-    }
-    if (wave) {
-#pragma unroll
-        for (int mi = 0; mi < MI; ++mi)
-#pragma unroll
-            for (int ni = 0; ni < NI; ++ni)
-#pragma unroll
-                for (int q = 0; q < 16; ++q) red[wave - 1][mi * NI + ni][q][lane] = acc[mi][ni][q];
-    }
-    __syncthreads();
-    if (wave) return;
-    const float* __restrict__ res = p.res[blockIdx.z];
-    const float* __restrict__ gate = p.gate[blockIdx.z];
-#pragma unroll
-    for (int mi = 0; mi < MI; ++mi)
-#pragma unroll
-        for (int ni = 0; ni < NI; ++ni) {
-            const int j = j0 + 32 * ni;
-#pragma unroll
-            for (int q = 0; q < 16; ++q) {
-                float v = acc[mi][ni][q];
-#pragma unroll
-                for (int w = 0; w < SLICES - 1; ++w) v += red[w][mi * NI + ni][q][lane];
-                const int row = blockIdx.y * (32 * MI) + 32 * mi + (q & 3) + 8 * (q >> 2) + 4 * h;
-                if (row < M && j < N) {
-                    if (res) v = res[(long long)row * ldc + j] + v;
-                    if (gate) v = gate[(long long)row * ldg + j] > 0.f ? v * gate_scale : 0.f;
-                    c[(long long)row * ldc + j] = v;
-                }
-            }
-        }
-}
-
-// The data gradient (A_T false): 32 batch rows x 32 inputs per workgroup, the contraction over the layer's outputs in 8 slices -- m is a few
-// hundred rows at most, so small tiles and the slices are what fills the chip.  The weight gradient (A_T true): 64 x 64 per workgroup (each operand value feeds two
-// MFMAs), 4 slices of the num_stages * m rows.  Both splits are fixed: they do not depend on m.
+// nb problems of one shape through csrc/grad_mm.h: no window, one accumulator set, the IEF's row strides and keep_scale in the gate
 template <bool A_T>
 static int mm_launch(const MmPtrs& p, int nb, int M, int N, int K, int lda, int ldb, int ldc, int ldg, float gate_scale, hipStream_t s) {
-    constexpr int MI = A_T ? 2 : 1, NI = A_T ? 2 : 1, SLICES = A_T ? 4 : 8;
-    if (!A_T && (K % 16 || lda % 4)) { hmmr_set_error("ief_mm_kernel: a row-major A needs K %% 16 == 0 and lda %% 4 == 0"); return -2; }
-    hipLaunchKernelGGL((ief_mm_kernel<A_T, MI, NI, SLICES>), dim3((unsigned)((N + 32 * NI - 1) / (32 * NI)), (unsigned)((M + 32 * MI - 1) / (32 * MI)), (unsigned)nb),
-                       dim3(64 * SLICES), 0, s, p, M, N, K, lda, ldb, ldc, ldg, gate_scale);
-    HMMR_CHECK_HIP(hipGetLastError());
-    return 0;
+    return grad_mm_launch<A_T, false, true, 1>("ief_mm_kernel", p, nb, M, N, K, lda, ldb, ldc, ldg, gate_scale, MmWindow{}, s);
 }
 
 // ---------------------------------------------------------------------------------------------------------------- the workspace
@@ -337,21 +175,10 @@ static bool ief_grouped(const hmmr_ief_weights_t* w, Strides (&st)[4]) {
     return true;
 }
 
-static hmmr_conv_desc_t fc_desc(const void* in, int m, int k, const hmmr_layer_t& l, void* out, int cout, int ldo, void* sk = nullptr,
-                                size_t skbytes = 0) {
-    hmmr_conv_desc_t d = {};
-    d.in = in; d.w = l.w; d.scale = l.scale; d.shift = l.shift; d.out = out;
-    d.in_dtype = HMMR_F32; d.out_dtype = HMMR_F32;
-    d.n_img = m; d.hin = d.win = 1; d.cin = k;
-    d.in_img_stride = k; d.in_row_stride = k; d.in_px_stride = k;
-    d.kh = d.kw = 1; d.sy = d.sx = 1; d.ho = d.wo = 1; d.cout = cout; d.ldo = ldo;
-    if (sk) { d.split_k = IEF_SPLIT_K; d.ws = sk; d.ws_bytes = skbytes; }
-    return d;
-}
-
 // ---------------------------------------------------------------------------------------------------------------- the forward
 // Both entry points run this.  It leaves in every regressor's set: pre, the masked h1 / h2 of every stage, theta_0 .. theta_S; and the
-// omegas in `omegas` [R][m][85].  The GEMMs are csrc/ief.hip's launches (hmmr_conv_gemm, HMMR_F32), so keep == NULL is hmmr_ief_fwd_from.
+// omegas in `omegas` [R][m][85].  The GEMMs are csrc/ief.hip's launches (csrc/tail_sched.h's fc_desc with HMMR_F32), so keep == NULL is
+// hmmr_ief_fwd_from.
 static int ief_train_forward(const hmmr_ief_weights_t* w, const float* strips, const float* omega_start, const unsigned char* keep,
                              float keep_scale, int m, float* omegas, const IefGradBufs& L, char* base, bool grouped, const Strides (&st)[4],
                              hipStream_t s) {
@@ -381,12 +208,12 @@ static int ief_train_forward(const hmmr_ief_weights_t* w, const float* strips, c
             hipLaunchKernelGGL(ief_train_init_theta_kernel, dim3(gth, nb), dim3(256), 0, s, dsrc, ld_d, w->no_optcam ? 0 : 3, nd_delta, th, m,
                                S + 1, set_f);
         HMMR_CHECK_HIP(hipGetLastError());
-        hmmr_conv_desc_t d = fc_desc(strips, m, 2048, Rg.fc1_phi, pre, 1024, 1024, base + L.sk, L.skbytes);
+        hmmr_conv_desc_t d = fc_desc(strips, HMMR_F32, m, 2048, Rg.fc1_phi, pre, HMMR_F32, 1024, 1024, IEF_SPLIT_K, base + L.sk, L.skbytes);
         group(d, st[0], false, false);
         if (hmmr_conv_gemm(&d, s)) return -2;
         for (int t = 0; t < S; ++t) {
             float* th_t = th + t * narrow; float* h1_t = h1 + t * wide; float* h2_t = h2 + t * wide;
-            d = fc_desc(th_t, m, LDT, Rg.fc1_theta, h1_t, 1024, 1024);
+            d = fc_desc(th_t, HMMR_F32, m, LDT, Rg.fc1_theta, h1_t, HMMR_F32, 1024, 1024);
             d.res = pre; d.ldr = 1024; d.relu = 1;
             group(d, st[1], true, true);
             if (hmmr_conv_gemm(&d, s)) return -2;
@@ -395,7 +222,7 @@ static int ief_train_forward(const hmmr_ief_weights_t* w, const float* strips, c
                                    keep_scale, wide, set_f, keep_reg);
                 HMMR_CHECK_HIP(hipGetLastError());
             }
-            d = fc_desc(h1_t, m, 1024, Rg.fc2, h2_t, 1024, 1024, base + L.sk, L.skbytes);
+            d = fc_desc(h1_t, HMMR_F32, m, 1024, Rg.fc2, h2_t, HMMR_F32, 1024, 1024, IEF_SPLIT_K, base + L.sk, L.skbytes);
             d.relu = 1;
             group(d, st[2], true, false);
             if (hmmr_conv_gemm(&d, s)) return -2;
@@ -404,12 +231,12 @@ static int ief_train_forward(const hmmr_ief_weights_t* w, const float* strips, c
                                    keep_scale, wide, set_f, keep_reg);
                 HMMR_CHECK_HIP(hipGetLastError());
             }
-            d = fc_desc(h2_t, m, 1024, Rg.fc3, th_t + narrow, Rg.nd, LDT, base + L.sk, L.skbytes);
+            d = fc_desc(h2_t, HMMR_F32, m, 1024, Rg.fc3, th_t + narrow, HMMR_F32, Rg.nd, LDT, IEF_SPLIT_K, base + L.sk, L.skbytes);
             d.res = th_t; d.ldr = LDT;
             group(d, st[3], true, true);
             if (hmmr_conv_gemm(&d, s)) return -2;
         }
-        hipLaunchKernelGGL(ief_train_finalize_kernel, dim3(gfin, nb), dim3(256), 0, s, (const float*)(th + S * narrow), dsrc, ld_d,
+        hipLaunchKernelGGL(ief_finalize_kernel, dim3(gfin, nb), dim3(256), 0, s, (const float*)(th + S * narrow), dsrc, ld_d,
                            r == 0 ? 0 : (w->no_optcam ? 2 : 1), omegas + (size_t)r * m * 85, m, set_f);
         HMMR_CHECK_HIP(hipGetLastError());
         return 0;
@@ -510,10 +337,7 @@ extern "C" int hmmr_ief_bwd(const hmmr_ief_weights_t* w, const hmmr_ief_bwd_desc
         auto bias = [&](size_t a_off, long long a_skip, int N, float* hmmr_ief_reg_grads_t::*out) -> int {
             CsPtrs p = {}; bool q = false;
             for (int z = 0; z < nb; ++z) { p.a[z] = F(r + z, a_off) + a_skip; p.out[z] = d->reg[r + z].*out; q = q || p.out[z]; }
-            if (!q) return 0;
-            hipLaunchKernelGGL(ief_colsum_kernel, dim3((unsigned)((N + 31) / 32), nb), dim3(256), 0, s, p, S * m, N, N);
-            HMMR_CHECK_HIP(hipGetLastError());
-            return 0;
+            return q ? grad_colsum_launch(p, nb, S * m, N, N, s) : 0;
         };
         if (bias(L.dth, narrow, LDT, &hmmr_ief_reg_grads_t::d_b3)) return -2;
         if (bias(L.da2, 0, 1024, &hmmr_ief_reg_grads_t::d_b2)) return -2;

@@ -6,223 +6,42 @@
 // Nothing is kept from a forward call: both entry points recompute the forward into their workspace with the launches of
 // csrc/temporal.hip (hmmr_groupnorm_relu, hmmr_conv_gemm with its split-K), except the last layer's output, which no gradient reads.
 //
-// One contraction kernel on v_mfma_f32_32x32x2_f32 (movie_mm_kernel; csrc/ief_grad.hip's ief_mm_kernel with a tap in the addressing):
-// the data gradient dH[r][ci] = sum_tap sum_co dY[r + 1 - tap][co] W[co][tap*2048 + ci] reads the bank as it lies in memory -- B[k][j] is
-// W[co][tap*2048 + j], rows of `co` at column offset tap*2048 with ldb = 6144, no transposed copy of the filters -- and dY with a row
-// shift per tap and a window guard; the weight gradient dW[co][tap*2048 + ci] = sum_r dY[r][co] h[r + tap - 1][ci] reads both operands by
-// row, the h rows shifted per tap and guarded by the window.  A guarded-out value is a zero operand.  Every output tile is one workgroup
-// whose waves each take a fixed slice of the contraction; the partial tiles are added in slice order.  No atomics anywhere.
+// The contractions go through csrc/grad_mm.h's kernel with a window: the data gradient dH[r][ci] = sum_tap sum_co dY[r + 1 - tap][co]
+// W[co][tap*2048 + ci] reads the bank as it lies in memory -- B[k][j] is W[co][tap*2048 + j], rows of `co` at column offset tap*2048 with
+// ldb = 6144, no transposed copy of the filters -- and dY with a row shift per tap and a window guard; the weight gradient
+// dW[co][tap*2048 + ci] = sum_r dY[r][co] h[r + tap - 1][ci] reads both operands by row, the h rows shifted per tap and guarded by the
+// window.  The recomputed forward is built from csrc/tail_sched.h, as csrc/temporal.hip's is.  No atomics anywhere.
 #include "common.h"
+#include "grad_mm.h"
 #include "hmmr_hip.h"
+#include "tail_sched.h"
 #include "workspace.h"
 
-static constexpr int C = 2048;                  // channels of phi, of every layer of both modules
-static constexpr int GROUPS = 32, CPG = C / GROUPS;
-static constexpr float GN_EPS = 1e-6f;          // csrc/temporal.hip
-static constexpr int TEMPORAL_SPLIT_K = 4;      // what hmmr_temporal_fwd / hmmr_hallucinator_fwd give hmmr_conv_gemm on an HMMR_F32 bank
-static constexpr int HAL_SPLIT_K = 4;
+static constexpr int C = TAIL_C;                // channels of phi, of every layer of both modules
+static constexpr int GROUPS = GN_GROUPS, CPG = C / GROUPS;
 
 // ---------------------------------------------------------------------------------------------------------------- the contraction
-// C[M][N] = sum_k A(i, k) * B(k, j)  (+ res[i][j]; then gated by gate[i][j] > 0), `taps` = 1 or 3, t = rows of a window, c0 = taps / 2.
-//   A_T false (data gradient): K = taps * kt.  k = tap * kt + co:  A(i, k) = a[i + c0 - tap][co] if that row lies in i's window,
-//                              B(k, j) = b[co][tap * kt + j].
-//   A_T true (weight gradient): N = taps * nt.  j = tap * nt + ci:  A(i, k) = a[k][i],  B(k, j) = b[k + tap - c0][ci] if that row lies
-//                              in k's window.
-// Workgroup = one (32 MI) x (32 NI) tile of C, wave w = slice w of the contraction (ks values each, a multiple of 16; a chunk of 16 lies
-// inside one tap); the partial tiles are added in slice order, (((w0 + w1) + w2) + ...).  v_mfma_f32_32x32x2_f32: lane l holds
-// A[i = l & 31][k = l >> 5] and B[k = l >> 5][j = l & 31]; result register q of lane l is C[(q & 3) + 8 (q >> 2) + 4 (l >> 5)][l & 31].
-// Step s of a chunk of 16 takes k0 + s (lanes 0..31) and k0 + 8 + s (lanes 32..63), so that a row-major A is read as two 16-byte pieces
-// per lane.  Eight steps of operands are loaded while the MFMAs of the eight before them run (two register sets).  Every read is
-// guarded by the operand's own extent and by the window.
-struct MmArgs {
-    const float* a; const float* b; float* c; const float* res; const float* gate;
-    int M, N, K, lda, ldb, ldc, taps, span, t;      // span = kt (A_T false) or nt (A_T true)
-};
-
-template <bool A_T, int MI, int NI, int SLICES>
-__global__ __launch_bounds__(64 * SLICES) void movie_mm_kernel(MmArgs p) {
-    static_assert((SLICES - 1) * MI * NI * 16 * 64 * 4 <= 64 * 1024, "the partial tiles must fit the static LDS limit");
-    __shared__ float red[SLICES - 1][MI * NI][16][64];
-    const float* __restrict__ a = p.a;
-    const float* __restrict__ b = p.b;
-    const int M = p.M, N = p.N, K = p.K, lda = p.lda, ldb = p.ldb, span = p.span, t = p.t, c0 = p.taps >> 1;
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const int r = lane & 31, h = lane >> 5;
-    const int i0 = blockIdx.y * (32 * MI) + r, j0 = blockIdx.x * (32 * NI) + r;
-    const int ks = ((K + SLICES - 1) / SLICES + 15) & ~15;
-    const int kb = wave * ks, ke = min(K, kb + ks);
-    // the data gradient's long contraction goes to two accumulators, the chunks of 16 in turn (half the length of a rounding chain, and
-    // no MFMA waits for the one before it); they are added once, in front of the slices
-    constexpr int SETS = A_T ? 1 : 2;
-    f32x16 accs[SETS][MI][NI];
-#pragma unroll
-    for (int e = 0; e < SETS; ++e)
-#pragma unroll
-        for (int mi = 0; mi < MI; ++mi)
-#pragma unroll
-            for (int ni = 0; ni < NI; ++ni)
-#pragma unroll
-                for (int q = 0; q < 16; ++q) accs[e][mi][ni][q] = 0.f;
-    // what does not change along the contraction: the position of an A row in its window (data gradient), the tap of a B column (weight gradient)
-    int it[MI], jtap[NI], jcol[NI];
-#pragma unroll
-    for (int mi = 0; mi < MI; ++mi) it[mi] = (i0 + 32 * mi) % t;
-#pragma unroll
-    for (int ni = 0; ni < NI; ++ni) {
-        const int j = j0 + 32 * ni;
-        jtap[ni] = A_T ? j / span : 0;
-        jcol[ni] = A_T ? j - jtap[ni] * span : j;
-    }
-    float a0[8][MI], b0[8][NI], a1[8][MI], b1[8][NI];
-    auto load = [&](float (&av)[8][MI], float (&bv)[8][NI], int k0) {
-        if (!A_T) {                                     // a lane's eight values are consecutive in its row: two 16-byte reads
-            const int tap = k0 / span, co = k0 - tap * span + 8 * h, sh = c0 - tap;
-#pragma unroll
-            for (int mi = 0; mi < MI; ++mi) {
-                const int i = i0 + 32 * mi;
-                f32x4 lo = {0.f, 0.f, 0.f, 0.f}, hi = lo;
-                if (k0 < ke && i < M && (unsigned)(it[mi] + sh) < (unsigned)t) {
-                    const f32x4* q = (const f32x4*)(a + (long long)(i + sh) * lda + co);
-                    lo = q[0]; hi = q[1];
-                }
-#pragma unroll
-                for (int s = 0; s < 4; ++s) { av[s][mi] = lo[s]; av[4 + s][mi] = hi[s]; }
-            }
-#pragma unroll
-            for (int s = 0; s < 8; ++s) {
-                const bool kok = k0 + 8 * h + s < ke;
-#pragma unroll
-                for (int ni = 0; ni < NI; ++ni)
-                    bv[s][ni] = (kok && j0 + 32 * ni < N) ? b[(long long)(co + s) * ldb + tap * span + jcol[ni]] : 0.f;
-            }
-        } else {
-#pragma unroll
-            for (int s = 0; s < 8; ++s) {
-                const int k = k0 + 8 * h + s;
-                const bool kok = k < ke;
-                const int kt = k % t;
-#pragma unroll
-                for (int mi = 0; mi < MI; ++mi) {
-                    const int i = i0 + 32 * mi;
-                    av[s][mi] = (kok && i < M) ? a[(long long)k * lda + i] : 0.f;
-                }
-#pragma unroll
-                for (int ni = 0; ni < NI; ++ni) {
-                    const int sh = jtap[ni] - c0;
-                    bv[s][ni] = (kok && j0 + 32 * ni < N && (unsigned)(kt + sh) < (unsigned)t) ? b[(long long)(k + sh) * ldb + jcol[ni]] : 0.f;
-                }
-            }
-        }
-    };
-    auto mma = [&](const float (&av)[8][MI], const float (&bv)[8][NI], f32x16 (&acc)[MI][NI]) {
-#pragma unroll
-        for (int s = 0; s < 8; ++s)
-#pragma unroll
-            for (int mi = 0; mi < MI; ++mi)
-#pragma unroll
-                for (int ni = 0; ni < NI; ++ni) acc[mi][ni] = __builtin_amdgcn_mfma_f32_32x32x2f32(av[s][mi], bv[s][ni], acc[mi][ni], 0, 0, 0);
-    };
-    load(a0, b0, kb);
-    for (int k0 = kb; k0 < ke; k0 += 32) {                  // (kb, ke and every branch below are the same for a whole wave)
-        if (k0 + 16 < ke) load(a1, b1, k0 + 16);
-        mma(a0, b0, accs[0]);
-        if (k0 + 16 < ke) {
-            if (k0 + 32 < ke) load(a0, b0, k0 + 32);
-            mma(a1, b1, accs[SETS - 1]);
-        }
-    }
-    f32x16 (&acc)[MI][NI] = accs[0];
-    if (SETS == 2) {
-#pragma unroll
-        for (int mi = 0; mi < MI; ++mi)
-#pragma unroll
-            for (int ni = 0; ni < NI; ++ni)
-#pragma unroll
-                for (int q = 0; q < 16; ++q) acc[mi][ni][q] += accs[SETS - 1][mi][ni][q];
-    }
-    if (wave) {
-#pragma unroll
-        for (int mi = 0; mi < MI; ++mi)
-#pragma unroll
-            for (int ni = 0; ni < NI; ++ni)
-#pragma unroll
-                for (int q = 0; q < 16; ++q) red[wave - 1][mi * NI + ni][q][lane] = acc[mi][ni][q];
-    }
-    __syncthreads();
-    if (wave) return;
-    float* __restrict__ c = p.c;
-    const float* __restrict__ res = p.res;
-    const float* __restrict__ gate = p.gate;
-    const int ldc = p.ldc;
-#pragma unroll
-    for (int mi = 0; mi < MI; ++mi)
-#pragma unroll
-        for (int ni = 0; ni < NI; ++ni) {
-            const int j = j0 + 32 * ni;
-#pragma unroll
-            for (int q = 0; q < 16; ++q) {
-                float v = acc[mi][ni][q];
-#pragma unroll
-                for (int w = 0; w < SLICES - 1; ++w) v += red[w][mi * NI + ni][q][lane];
-                const int row = blockIdx.y * (32 * MI) + 32 * mi + (q & 3) + 8 * (q >> 2) + 4 * h;
-                if (row < M && j < N) {
-                    if (res) v = res[(long long)row * ldc + j] + v;
-                    if (gate) v = gate[(long long)row * ldc + j] > 0.f ? v : 0.f;
-                    c[(long long)row * ldc + j] = v;
-                }
-            }
-        }
-}
-
-// The data gradient: 32 rows x 32 inputs per workgroup, the contraction over (tap, output channel) in 8 slices -- b*t is a few hundred
-// rows at most, so small tiles and the slices are what fills the chip; the split is fixed, it does not depend on the rows.
+// One problem per launch (MmOne, CsOne: no pointer tables).
+// The data gradient: the contraction over (tap, output channel), in two accumulator sets (csrc/grad_mm.h); a window's rows never meet
+// another's.  t = rows of a window (a fully-connected layer: one tap, every row a window of its own).  The gate is the plain h > 0.
 //   dx[rows][C] = sum_tap dy[row + c0 - tap] . W[:, tap]   (+ res, gated)
 static int data_grad(const float* dy, const float* w, int rows, int taps, int t, const float* res, const float* gate, float* dx, hipStream_t s) {
-    MmArgs p = {dy, w, dx, res, gate, rows, C, taps * C, C, taps * C, C, taps, C, t};
-    hipLaunchKernelGGL((movie_mm_kernel<false, 1, 1, 8>), dim3(C / 32, (unsigned)((rows + 31) / 32)), dim3(64 * 8), 0, s, p);
-    HMMR_CHECK_HIP(hipGetLastError());
-    return 0;
+    const MmOne p = {dy, w, dx, res, gate};
+    return grad_mm_launch<false, true, false, 2>("movie_grad data_grad", p, 1, rows, C, taps * C, C, taps * C, C, C, 1.f, MmWindow{taps, C, t}, s);
 }
-// The weight gradient: 64 x 64 per workgroup (each operand value feeds two MFMAs; a tile lies inside one tap), 4 slices of the rows.
+// The weight gradient, one accumulator set:
 //   dw[C][taps * C] = sum_rows dy[row][co] h[row + tap - c0][ci]
 static int weight_grad(const float* dy, const float* h, int rows, int taps, int t, float* dw, hipStream_t s) {
-    MmArgs p = {dy, h, dw, nullptr, nullptr, C, taps * C, rows, C, C, taps * C, taps, C, t};
-    hipLaunchKernelGGL((movie_mm_kernel<true, 2, 2, 4>), dim3((unsigned)(taps * C / 64), C / 64), dim3(64 * 4), 0, s, p);
-    HMMR_CHECK_HIP(hipGetLastError());
-    return 0;
+    const MmOne p = {dy, h, dw, nullptr, nullptr};
+    return grad_mm_launch<true, true, false, 1>("movie_grad weight_grad", p, 1, C, taps * C, rows, C, C, taps * C, taps * C, 1.f, MmWindow{taps, C, t}, s);
 }
-
-// out[col] = sum over the K rows of a[K][C], accumulated in double and rounded once (csrc/ief_grad.hip's column sum, DESIGN 4.14: a plain
-// fp32 chain over the rows loses bits a blocked sum keeps).  A workgroup owns 32 columns; thread (g, c) adds rows g, g + 8, ... of column
-// c in row order, thread (0, c) adds the eight partial sums in g order: a fixed order for a given K.
-__global__ __launch_bounds__(256) void movie_colsum_kernel(const float* __restrict__ a, int K, float* __restrict__ out) {
-    __shared__ double part[8][32];
-    const int c = threadIdx.x & 31, g = threadIdx.x >> 5;
-    const int col = blockIdx.x * 32 + c;                // (C is a multiple of 32: every column exists)
-    double v = 0.0;
-    for (int k = g; k < K; k += 8) v += (double)a[(long long)k * C + col];
-    part[g][c] = v;
-    __syncthreads();
-    if (g) return;
-    for (int q = 1; q < 8; ++q) v += part[q][c];
-    out[col] = (float)v;
-}
+// out[C] = the column sum of a[rows][C] (a bias gradient), in double
 static int col_sum(const float* a, int rows, float* out, hipStream_t s) {
-    hipLaunchKernelGGL(movie_colsum_kernel, dim3(C / 32), dim3(256), 0, s, a, rows, out);
-    HMMR_CHECK_HIP(hipGetLastError());
-    return 0;
+    const CsOne<C> p = {a, out};
+    return grad_colsum_launch(p, 1, rows, C, C, s);
 }
 
 // ---------------------------------------------------------------------------------------------------------------- GroupNorm + ReLU backward
-__device__ __forceinline__ float gn_block_sum(float v, float* red) {          // csrc/temporal.hip's block_sum_256: the forward's order
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
-    __syncthreads();
-    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
-    __syncthreads();
-    return red[0] + red[1] + red[2] + red[3];
-}
-
 // One workgroup per (window b, group g), like the forward's.  x: the GN input, h = relu(GN(x)) as the forward stored it (the gate),
 // dh: the cotangent of h.  Mean and rstd are recomputed in the forward's two-pass form; with g = dh * (h > 0) * gamma and
 // xhat = (x - mean) * rstd:   dx = rstd * (g - mean(g) - xhat * mean(g * xhat))  (+ res), the means over t x 64.
@@ -241,13 +60,13 @@ __global__ __launch_bounds__(256) void gn_relu_bwd_kernel(const float* __restric
     const float* db = dh + base;
     float s = 0.f;
     for (int i = threadIdx.x; i < cnt; i += 256) s += xb[(i / CPG) * C + (i % CPG)];
-    const float mean = gn_block_sum(s, red) / (float)cnt;
+    const float mean = block_sum_256(s, red) / (float)cnt;
     float q = 0.f;
     for (int i = threadIdx.x; i < cnt; i += 256) {
         const float d = xb[(i / CPG) * C + (i % CPG)] - mean;
         q += d * d;
     }
-    const float var = gn_block_sum(q, red) / (float)cnt;
+    const float var = block_sum_256(q, red) / (float)cnt;
     const float rstd = rsqrtf(var + GN_EPS);
     const int ch = threadIdx.x % CPG;                   // 256 % 64 == 0: a thread stays on one channel
     const float gm = gamma[g * CPG + ch];
@@ -258,8 +77,8 @@ __global__ __launch_bounds__(256) void gn_relu_bwd_kernel(const float* __restric
         s1 += gv;
         s2 += gv * ((xb[o] - mean) * rstd);
     }
-    const float m1 = gn_block_sum(s1, red) / (float)cnt;
-    const float m2 = gn_block_sum(s2, red) / (float)cnt;
+    const float m1 = block_sum_256(s1, red) / (float)cnt;
+    const float m2 = block_sum_256(s2, red) / (float)cnt;
     if (dx) {
         float* ob = dx + base;
         const float* rb = res ? res + base : nullptr;
@@ -328,7 +147,7 @@ static TemporalGradBufs temporal_grad_layout(int b, int t, int num_blocks) {
     }
     l.dy[0] = c.take(rows); l.dy[1] = c.take(rows); l.dh = c.take(rows); l.dc1 = c.take(rows);
     l.pg = c.take((size_t)b * C * 8); l.pb = c.take((size_t)b * C * 8);
-    l.skbytes = hmmr_conv_splitk_workspace_bytes(b * t, C, TEMPORAL_SPLIT_K);
+    l.skbytes = hmmr_conv_splitk_workspace_bytes(b * t, C, temporal_split_k(HMMR_F32));
     l.sk = c.take(l.skbytes);
     l.total = c.total();
     return l;
@@ -354,16 +173,9 @@ extern "C" size_t hmmr_hallucinator_bwd_workspace_bytes(int m) { return m > 0 ? 
 static bool plain_f32(const hmmr_layer_t& l) { return l.w && l.shift && !l.scale; }
 
 // ---------------------------------------------------------------------------------------------------------------- the temporal encoder
-// one convolution of csrc/temporal.hip's forward: the descriptor hmmr_temporal_fwd builds, on fp32 operands
+// one convolution of the forward on fp32 operands: csrc/temporal.hip's descriptor
 static int temporal_conv(const float* in, const hmmr_layer_t& l, const float* res, float* out, int b, int t, void* sk, size_t skbytes, hipStream_t s) {
-    hmmr_conv_desc_t d = {};
-    d.in = in; d.w = l.w; d.scale = l.scale; d.shift = l.shift; d.tile = l.tile;
-    d.out = out; d.in_dtype = HMMR_F32; d.out_dtype = HMMR_F32;
-    d.n_img = b; d.hin = t; d.win = 1; d.cin = C;
-    d.in_img_stride = (int64_t)t * C; d.in_row_stride = C; d.in_px_stride = C;
-    d.kh = 3; d.kw = 1; d.sy = d.sx = 1; d.py = 1; d.px = 0; d.ho = t; d.wo = 1; d.cout = C; d.ldo = C;
-    d.split_k = TEMPORAL_SPLIT_K; d.ws = sk; d.ws_bytes = skbytes;
-    d.res = res; d.ldr = C;
+    const hmmr_conv_desc_t d = temporal_conv_desc(in, HMMR_F32, l, res, out, b, t, sk, skbytes);
     return hmmr_conv_gemm(&d, s) ? -2 : 0;
 }
 
@@ -432,15 +244,9 @@ extern "C" int hmmr_temporal_bwd(const hmmr_temporal_weights_t* w, const hmmr_te
 }
 
 // ---------------------------------------------------------------------------------------------------------------- the hallucinator
+// a hidden layer of the forward on fp32 operands: csrc/temporal.hip's descriptor, relu, no residual
 static int hal_fc(const float* in, const hmmr_layer_t& l, float* out, int m, void* sk, size_t skbytes, hipStream_t s) {
-    hmmr_conv_desc_t d = {};
-    d.in = in; d.w = l.w; d.scale = l.scale; d.shift = l.shift; d.out = out;
-    d.in_dtype = HMMR_F32; d.out_dtype = HMMR_F32;
-    d.n_img = m; d.hin = d.win = 1; d.cin = C;
-    d.in_img_stride = C; d.in_row_stride = C; d.in_px_stride = C;
-    d.kh = d.kw = 1; d.sy = d.sx = 1; d.ho = d.wo = 1; d.cout = C; d.ldo = C;
-    d.relu = 1; d.ldr = C;
-    d.split_k = HAL_SPLIT_K; d.ws = sk; d.ws_bytes = skbytes;
+    const hmmr_conv_desc_t d = hal_fc_desc(in, HMMR_F32, l, out, HMMR_F32, m, 1, nullptr, sk, skbytes);
     return hmmr_conv_gemm(&d, s) ? -2 : 0;
 }
 

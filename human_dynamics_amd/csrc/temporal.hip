@@ -8,25 +8,8 @@
 // only the GEMM operands take the struct's dtype.
 #include "common.h"
 #include "hmmr_hip.h"
+#include "tail_sched.h"
 #include "workspace.h"
-
-#define GN_EPS 1e-6f
-// K = 3*2048 is long and M = b*t is short (640 rows for 32 windows): 4 K-slices quadruple the
-// number of workgroups.  Fixed per layer and operand mode, never derived from b, so a window's result does not
-// depend on how many windows share the launch.  Split operands: 5 slices of the 128x256 ring tile (40 tiles x 5 = 200
-// workgroups on 256 CUs, 39 K steps each) measured 0.427 ms per f_movie pass of 32 windows against 0.477 for 4 slices
-// of the 256x128 tile (tools/stage_bench.py, round 3; 6 / 8 slices and the two-stage tiles are slower).
-#define TEMPORAL_SPLIT_K_MAX 5
-static inline int temporal_split_k(int dtype) { return dtype == HMMR_F16X3 ? 5 : 4; }
-
-__device__ __forceinline__ float block_sum_256(float v, float* red) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
-    __syncthreads();                       // protect `red` from the previous use
-    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
-    __syncthreads();
-    return red[0] + red[1] + red[2] + red[3];
-}
 
 // One workgroup per (window b, group g).  tf.contrib.layers.group_norm with
 // reduction_axes=(-3,-2) on [b,t,1,c]: mean and POPULATION variance over
@@ -112,7 +95,7 @@ extern "C" int hmmr_temporal_fwd(const hmmr_temporal_weights_t* w, const float* 
     HMMR_REQUIRE(w->num_blocks >= 1 && w->num_blocks <= HMMR_MAX_TEMPORAL_BLOCKS, "hmmr_temporal_fwd: bad num_blocks");
     const MovieBufs L = temporal_layout(b, t, w->dtype);
     HMMR_REQUIRE(ws_bytes >= L.total, "hmmr_temporal_fwd: workspace too small");
-    const int C = 2048;
+    constexpr int C = TAIL_C;
     char* base = (char*)ws;
     void* h = base + L.buf[0];
     float *h1 = (float*)(base + L.buf[1]), *net[2] = {(float*)(base + L.buf[2]), (float*)(base + L.buf[3])};
@@ -120,18 +103,11 @@ extern "C" int hmmr_temporal_fwd(const hmmr_temporal_weights_t* w, const float* 
     for (int i = 0; i < w->num_blocks; ++i) {
         const hmmr_temporal_block_t& B = w->block[i];
         float* dst = (i == w->num_blocks - 1) ? strips : net[i & 1];
-        if (hmmr_groupnorm_relu(cur, B.gn1_gamma, B.gn1_beta, b, t, C, 32, h, w->dtype, stream)) return -2;
-        hmmr_conv_desc_t d = {};
-        d.in = h; d.w = B.conv1.w; d.scale = B.conv1.scale; d.shift = B.conv1.shift; d.tile = B.conv1.tile;
-        d.out = h1; d.in_dtype = w->dtype; d.out_dtype = HMMR_F32;
-        d.n_img = b; d.hin = t; d.win = 1; d.cin = C;
-        d.in_img_stride = (int64_t)t * C; d.in_row_stride = C; d.in_px_stride = C;
-        d.kh = 3; d.kw = 1; d.sy = d.sx = 1; d.py = 1; d.px = 0; d.ho = t; d.wo = 1; d.cout = C; d.ldo = C;
-        d.split_k = temporal_split_k(w->dtype); d.ws = base + L.sk; d.ws_bytes = L.skbytes;
+        if (hmmr_groupnorm_relu(cur, B.gn1_gamma, B.gn1_beta, b, t, C, GN_GROUPS, h, w->dtype, stream)) return -2;
+        hmmr_conv_desc_t d = temporal_conv_desc(h, w->dtype, B.conv1, nullptr, h1, b, t, base + L.sk, L.skbytes);
         if (hmmr_conv_gemm(&d, stream)) return -2;
-        if (hmmr_groupnorm_relu(h1, B.gn2_gamma, B.gn2_beta, b, t, C, 32, h, w->dtype, stream)) return -2;
-        d.w = B.conv2.w; d.scale = B.conv2.scale; d.shift = B.conv2.shift; d.tile = B.conv2.tile;
-        d.res = cur; d.ldr = C; d.out = dst;            // residual adds the BLOCK INPUT (models.py:226)
+        if (hmmr_groupnorm_relu(h1, B.gn2_gamma, B.gn2_beta, b, t, C, GN_GROUPS, h, w->dtype, stream)) return -2;
+        d = temporal_conv_desc(h, w->dtype, B.conv2, cur, dst, b, t, base + L.sk, L.skbytes);      // residual adds the BLOCK INPUT (models.py:226)
         if (hmmr_conv_gemm(&d, stream)) return -2;
         cur = dst;
     }
@@ -160,7 +136,7 @@ extern "C" int hmmr_hallucinator_fwd(const hmmr_hallucinator_weights_t* w, const
     HMMR_REQUIRE(m > 0, "hmmr_hallucinator_fwd: m must be positive");
     const MovieBufs L = hallucinator_layout(m, w->dtype);
     HMMR_REQUIRE(ws_bytes >= L.total, "hmmr_hallucinator_fwd: workspace too small");
-    const int C = 2048;
+    constexpr int C = TAIL_C;
     char* base = (char*)ws;
     void *x = base + L.buf[0], *h1 = base + L.buf[1], *h2 = base + L.buf[2];
     hipStream_t s = (hipStream_t)stream;
@@ -175,14 +151,7 @@ extern "C" int hmmr_hallucinator_fwd(const hmmr_hallucinator_weights_t* w, const
         xin = x;
     }
     auto fc = [&](const void* in, const hmmr_layer_t& l, void* o, int odt, int relu, const float* res) {
-        hmmr_conv_desc_t d = {};
-        d.in = in; d.w = l.w; d.scale = l.scale; d.shift = l.shift; d.out = o;
-        d.in_dtype = w->dtype; d.out_dtype = odt;
-        d.n_img = m; d.hin = d.win = 1; d.cin = C;
-        d.in_img_stride = C; d.in_row_stride = C; d.in_px_stride = C;
-        d.kh = d.kw = 1; d.sy = d.sx = 1; d.ho = d.wo = 1; d.cout = C; d.ldo = C;
-        d.relu = relu; d.res = res; d.ldr = C;
-        d.split_k = 4; d.ws = base + L.sk; d.ws_bytes = L.skbytes;            // (the hallucinator keeps 4 slices in every mode)
+        hmmr_conv_desc_t d = hal_fc_desc(in, w->dtype, l, o, odt, m, relu, res, base + L.sk, L.skbytes);
         return hmmr_conv_gemm(&d, s);
     };
     if (fc(xin, w->fc1, h1, w->dtype, 1, nullptr)) return -2;

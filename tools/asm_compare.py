@@ -1,12 +1,16 @@
 #!/usr/bin/env python3
 """Compare the gfx950 assembly of two builds of one .hip file, kernel by kernel and whole.
 
-    python tools/asm_compare.py PARENT.s NEW.s [label]
+    python tools/asm_compare.py PARENT.s NEW.s [label] [--rename OLD=NEW ...]
 
 Both files come from `hipcc <flags of build.py> --save-temps -x hip -c csrc/FILE.hip` with the source at one and the same path (the
-*-hip-amdgcn-amd-amdhsa-gfx950.s file).  Symbol names are masked where a refactor may change them (the dump page, the compilation-unit
-id); everything else counts.  A kernel whose instruction stream differs is listed with its per-mnemonic histogram and its resource
-metadata next to the parent's; "renumbered" means equal histogram and equal metadata.  Exit status 1 when any kernel differs."""
+*-hip-amdgcn-amd-amdhsa-gfx950.s file).  Names are masked where a refactor may change them: the dump page, the compilation-unit id, and
+the function index of a basic-block label (.LBB<function>_<block> is compared as .LBB_<block>: the index counts the functions in front
+of the kernel, so removing or adding one above it renumbers every label below; the block number still counts).  Everything else counts.  A kernel whose instruction stream differs is listed with its per-mnemonic histogram and its resource
+metadata next to the parent's; "renumbered" means equal histogram and equal metadata.  --rename OLD=NEW reads the parent's file with the
+(mangled) symbol OLD spelled NEW, so that a kernel the refactor renamed is compared with its successor.  Exit status 1 when any kernel
+differs."""
+import argparse
 import collections
 import re
 import sys
@@ -17,16 +21,21 @@ KEYS = (".vgpr_count", ".agpr_count", ".sgpr_count", ".private_segment_fixed_siz
 def mask(line):
     line = line.split(";")[0].rstrip()
     line = re.sub(r"_ZN12_GLOBAL__N_1\d+g_\w*dump\w*E|_ZL\d+g_dump_page", "DUMP", line)
+    line = re.sub(r"\.LBB\d+_", ".LBB_", line)          # a block label counts the functions in front of it: a kernel removed above renumbers it
     return re.sub(r"__hip_cuid_[0-9a-f]+", "__hip_cuid_X", line)
 
 
-def parse(path):
+def parse(path, renames=()):
     """kernel name -> its instruction lines; kernel name -> resource metadata; all masked lines"""
-    text = open(path).read().split("\n")
+    text = open(path).read()
+    for old, new in renames:
+        text = re.sub(r"\b%s\b" % re.escape(old), new, text)
+    named = set(re.findall(r"^\s+\.name:\s+(_Z\w+)\s*$", text, re.M))      # the kernels of the metadata: a static one is _ZL...
+    text = text.split("\n")
     body, meta, cur, entry = collections.OrderedDict(), {}, None, None
     for ln in text:
         m = re.match(r"^(_Z\w+):", ln)
-        if m and cur is None and not m.group(1).startswith("_ZL"):
+        if m and cur is None and (m.group(1) in named or not m.group(1).startswith("_ZL")):
             cur = m.group(1)
             body[cur] = []
         elif cur is not None:
@@ -55,9 +64,20 @@ def histogram(lines):
 
 
 def main():
-    pa, ma, la = parse(sys.argv[1])
-    pb, mb, lb = parse(sys.argv[2])
-    label = sys.argv[3] if len(sys.argv) > 3 else sys.argv[2]
+    def pair(text):
+        old, eq, new = text.partition("=")
+        if not (old and eq and new):
+            raise argparse.ArgumentTypeError("expected OLD=NEW, got %r" % text)
+        return old, new
+    ap = argparse.ArgumentParser(description="compare the gfx950 assembly of two builds of one .hip file")
+    ap.add_argument("parent")
+    ap.add_argument("new")
+    ap.add_argument("label", nargs="?")
+    ap.add_argument("--rename", action="append", type=pair, default=[], metavar="OLD=NEW")
+    args = ap.parse_args()
+    pa, ma, la = parse(args.parent, args.rename)
+    pb, mb, lb = parse(args.new)
+    label = args.label or args.new
     missing = [k for k in pa if k not in pb] + [k for k in pb if k not in pa]
     renumbered, different = [], []
     for k in pa:
