@@ -180,6 +180,37 @@ class HallucinatorBwdDesc(C.Structure):
     _fields_ = [("phi", _fp), ("m", C.c_int), ("d_out", _fp), ("d_phi", _fp)] + [("d_" + k, _fp) for k in HALLUCINATOR_GRAD_NAMES]
 
 
+DISC_POSE_LAYERS = ("conv1", "conv2", "heads", "fc1", "fc2", "fc_out")
+DISC_POSE_GRAD_NAMES = ("conv1", "bc1", "conv2", "bc2", "heads", "bj", "fc1", "b1", "fc2", "b2", "fc_out", "bo")
+
+
+class Rows(C.Structure):
+    """hmmr_rows_t: a segment of rows {ptr, ld (floats per row), n}"""
+    _fields_ = [("ptr", _fp), ("ld", C.c_int64), ("n", C.c_int)]
+
+
+class DiscPoseWeights(C.Structure):
+    """hmmr_disc_pose_weights_t: the pose discriminator's HMMR_F32 bank (csrc/disc_pose.hip)"""
+    _fields_ = [("dtype", C.c_int)] + [(k, Layer) for k in DISC_POSE_LAYERS]
+
+
+class DiscPoseGrads(C.Structure):
+    """hmmr_disc_pose_grads_t: the twelve gradients in the layouts of the bank; each may be NULL"""
+    _fields_ = [("d_" + k, _fp) for k in DISC_POSE_GRAD_NAMES]
+
+
+class DiscPoseBwdDesc(C.Structure):
+    """hmmr_disc_pose_bwd_desc_t: one call of the pose discriminator's backward"""
+    _fields_ = [("rows_a", Rows), ("rows_b", Rows), ("d_out", _fp), ("d_poses_a", _fp), ("ld_a", C.c_int64), ("d_poses_b", _fp),
+                ("ld_b", C.c_int64), ("grads", DiscPoseGrads)]
+
+
+class PosePriorDesc(C.Structure):
+    """hmmr_pose_prior_desc_t: the closed loop of one step (losses, d_rs_fake, the gradients of w_d * d_pose)"""
+    _fields_ = [("real", Rows), ("fake", Rows), ("w_e", C.c_float), ("w_d", C.c_float), ("losses", _fp), ("d_rs_fake", _fp),
+                ("grads", DiscPoseGrads)]
+
+
 class SmplConsts(C.Structure):
     _fields_ = [("num_verts", C.c_int), ("num_kps", C.c_int), ("lbs_nnz", C.c_int), ("vpad", C.c_int),
                 ("dirs", _fp), ("j_template", _fp), ("j_shapedirs", _fp), ("parents", _ip),
@@ -343,6 +374,12 @@ SIGNATURES = {
     "hmmr_temporal_bwd": (C.c_int, [C.POINTER(TemporalWeights), C.POINTER(TemporalBwdDesc), _vp, C.c_size_t, _vp]),
     "hmmr_hallucinator_bwd_workspace_bytes": (C.c_size_t, [C.c_int]),
     "hmmr_hallucinator_bwd": (C.c_int, [C.POINTER(HallucinatorWeights), C.POINTER(HallucinatorBwdDesc), _vp, C.c_size_t, _vp]),
+    "hmmr_pack_disc_pose_bytes": (C.c_size_t, [C.POINTER(Var), C.c_int, C.c_int]),
+    "hmmr_pack_disc_pose": (C.c_int, [C.POINTER(Var), C.c_int, C.c_int, _vp, C.c_size_t, _vp, C.POINTER(DiscPoseWeights)]),
+    "hmmr_disc_pose_workspace_bytes": (C.c_size_t, [C.c_int]),
+    "hmmr_disc_pose_fwd": (C.c_int, [C.POINTER(DiscPoseWeights), C.POINTER(Rows), C.POINTER(Rows), _fp, _vp, C.c_size_t, _vp]),
+    "hmmr_disc_pose_bwd": (C.c_int, [C.POINTER(DiscPoseWeights), C.POINTER(DiscPoseBwdDesc), _vp, C.c_size_t, _vp]),
+    "hmmr_pose_prior": (C.c_int, [C.POINTER(DiscPoseWeights), C.POINTER(PosePriorDesc), _vp, C.c_size_t, _vp]),
     "hmmr_smpl_workspace_bytes": (C.c_size_t, [C.c_int]),
     "hmmr_smpl_fwd": (C.c_int, [C.POINTER(SmplConsts), _fp, C.c_int, _fp, C.c_int, _fp, C.c_int, C.c_int,
                                 _fp, _fp, _fp, _fp, _vp, C.c_size_t, _vp]),

@@ -619,6 +619,40 @@ void pack_ief(const Vars& v, int dtype, const int* delta_t, int n_delta, int num
     iw->no_optcam = nd_delta == 75 ? 1 : 0;
 }
 
+// ------------------------------------------------------------------------------------------------------------------ pose discriminator
+// [in][out] weights -> rows [R][K] (out <= R, in <= K), the rest zero: the small layers keep their own row counts, fc1's K = 736 is padded
+void fc_rows_padded(const float* w, int in, int out, int R, int K, std::vector<float>& rows) {
+    rows.assign((size_t)R * K, 0.f);
+    for (int k = 0; k < in; ++k)
+        for (int n = 0; n < out; ++n) rows[(size_t)n * K + k] = w[(size_t)k * out + n];
+}
+void pack_disc_pose(const Vars& v, int dtype, Blob& b, hmmr_disc_pose_weights_t* dw) {
+    memset(dw, 0, sizeof(*dw));
+    if (dtype != HMMR_F32) fail("the pose discriminator's bank is HMMR_F32 only (dtype " + std::to_string(dtype) + " given)");
+    dw->dtype = dtype;
+    const std::string p = "D_pose/";
+    std::vector<float> rows;
+    fc_rows_padded(v.get(p + "D_conv1/weights", 9 * 32), 9, 32, 32, 16, rows);
+    dw->conv1 = layer(b, rows, 32, 16, dtype, nullptr, 0, v.get(p + "D_conv1/biases", 32), 32);
+    fc_rows_padded(v.get(p + "D_conv2/weights", 32 * 32), 32, 32, 32, 32, rows);
+    dw->conv2 = layer(b, rows, 32, 32, dtype, nullptr, 0, v.get(p + "D_conv2/biases", 32), 32);
+    rows.assign((size_t)32 * 32, 0.f);
+    std::vector<float> bj(32, 0.f);
+    for (int j = 0; j < 23; ++j) {
+        const std::string q = p + "pose_out_j" + std::to_string(j);
+        const float* wj = v.get(q + "/weights", 32);
+        for (int c = 0; c < 32; ++c) rows[(size_t)j * 32 + c] = wj[c];
+        bj[j] = v.get(q + "/biases", 1)[0];
+    }
+    dw->heads = layer(b, rows, 32, 32, dtype, nullptr, 0, bj.data(), 32);
+    fc_rows_padded(v.get(p + "D_alljoints_fc1/weights", (int64_t)736 * 1024), 736, 1024, 1024, 1024, rows);
+    dw->fc1 = layer(b, rows, 1024, 1024, dtype, nullptr, 0, v.get(p + "D_alljoints_fc1/biases", 1024), 1024);
+    fc_rows_padded(v.get(p + "D_alljoints_fc2/weights", (int64_t)1024 * 1024), 1024, 1024, 1024, 1024, rows);
+    dw->fc2 = layer(b, rows, 1024, 1024, dtype, nullptr, 0, v.get(p + "D_alljoints_fc2/biases", 1024), 1024);
+    fc_rows_padded(v.get(p + "D_alljoints_out/weights", 1024), 1024, 1, 128, 1024, rows);
+    dw->fc_out = layer(b, rows, 128, 1024, dtype, nullptr, 0, v.get(p + "D_alljoints_out/biases", 1), 1);
+}
+
 // ------------------------------------------------------------------------------------------------------------------ SMPL
 void pack_smpl(const hmmr_smpl_source_t* s, int lsp, int split, Blob& b, hmmr_smpl_consts_t* sc) {
     memset(sc, 0, sizeof(*sc));
@@ -780,6 +814,15 @@ extern "C" int hmmr_pack_ief(const hmmr_var_t* vars, int n_vars, int dtype, cons
     if (!vars || !host_blob || !out || (n_delta > 0 && !delta_t)) { hmmr_set_error("hmmr_pack_ief: null argument"); return -1; }
     Blob b(host_blob, blob_bytes, device_base);
     return guarded("hmmr_pack_ief", b, [&] { pack_ief(Vars{vars, n_vars}, dtype, delta_t, n_delta, num_stages, b, out); });
+}
+extern "C" size_t hmmr_pack_disc_pose_bytes(const hmmr_var_t* vars, int n_vars, int dtype) {
+    return counted("hmmr_pack_disc_pose_bytes", [&](Blob& b) { hmmr_disc_pose_weights_t t; pack_disc_pose(Vars{vars, n_vars}, dtype, b, &t); });
+}
+extern "C" int hmmr_pack_disc_pose(const hmmr_var_t* vars, int n_vars, int dtype, void* host_blob, size_t blob_bytes, const void* device_base,
+                                   hmmr_disc_pose_weights_t* out) {
+    if (!vars || !host_blob || !out) { hmmr_set_error("hmmr_pack_disc_pose: null argument"); return -1; }
+    Blob b(host_blob, blob_bytes, device_base);
+    return guarded("hmmr_pack_disc_pose", b, [&] { pack_disc_pose(Vars{vars, n_vars}, dtype, b, out); });
 }
 extern "C" size_t hmmr_pack_smpl_bytes(const hmmr_smpl_source_t* src, int lsp, int split) {
     if (!src) return 0;

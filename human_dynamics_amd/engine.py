@@ -150,6 +150,9 @@ class HmmrEngine(object):
         # ... and that of f_movie (the temporal blocks and the hallucinator): movie_bank, the same way
         self._movie_source = {k: v for k, v in w.items() if k.startswith(("AZ_FC_block", "fc2_res/"))} if self.tw is not None else None
         self._movie_bank = None
+        # ... and the pose discriminator's (disc_pose_bank): the checkpoint's D_pose/* variables, when it has them
+        self._disc_source = {k: v for k, v in w.items() if k.startswith("D_pose/")}
+        self._disc_pose_bank = None
         # an all-fp32 engine is the exact-arithmetic reference (the probe's last rung, the saturation fallback): its SMPL blend product
         # stays on fp32 operands too, so nothing in it can clamp
         all_f32 = (self.dtype, self.temporal_dtype, self.ief_dtype) == (L.HMMR_F32,) * 3
@@ -647,6 +650,112 @@ class HmmrEngine(object):
         ws = self._movie_ws(nbytes)
         L.check(self.lib.hmmr_hallucinator_bwd(C.byref(bank.hw), C.byref(d), ws.data_ptr(), nbytes, self._stream()), "hmmr_hallucinator_bwd")
         return (d_phi.reshape(phi.shape) if d_phi is not None else None), g
+
+    # -- the pose discriminator (csrc/disc_pose.hip) -------------------------------
+    def disc_pose_bank(self, weights=None):
+        """The trainable pose-discriminator bank (disc_bank.PoseDiscBank): an HMMR_F32 pack whose twelve tensors are views of the
+        packed memory.  weights: a dict of checkpoint-named arrays (D_pose/*) that (re)places the bank; None = the bank there is, packed
+        on the first call from the engine's checkpoint -- an inference-only process never pays for it."""
+        if weights is not None or self._disc_pose_bank is None:
+            from .disc_bank import PoseDiscBank
+            src = weights if weights is not None else self._disc_source
+            if not src:
+                raise L.HmmrError("the loaded weights have no D_pose/* variables: pass them to disc_pose_bank(weights)")
+            self._disc_pose_bank = PoseDiscBank(src, self.device)
+        return self._disc_pose_bank
+
+    def _pose_rows(self, x, what):
+        """a segment of pose rows as (tensor kept alive, hmmr_rows_t): fp32 device rows of 207 values at any row stride >= 207 with
+        a unit inner stride are used in place -- [n,207], [n,23,9], [n,23,1,9], [n,23,3,3], or [n,24,...] / [n,216] from which the
+        global rotation is dropped as a view (Rs + 9, ld = 216)"""
+        r = L.Rows()
+        if x is None:
+            return None, r
+        if not (isinstance(x, torch.Tensor) and x.is_cuda and x.dtype == torch.float32):
+            x = self.to_device(x)
+        n = x.shape[0]
+        if n == 0:
+            return None, r
+        per = x[0].numel()
+        if per not in (207, 216):
+            raise ValueError("%s: rows of 207 (joints 1..23) or 216 (all 24 rotations) values, got %s" % (what, tuple(x.shape)))
+        inner = x[0]
+        if not inner.is_contiguous() or (n > 1 and x.stride(0) < per):
+            x = x.contiguous()
+        flat = x.as_strided((n, per), (x.stride(0) if n > 1 else per, 1), x.storage_offset())
+        if per == 216:
+            flat = flat[:, 9:]
+        r.ptr, r.ld, r.n = flat.data_ptr(), flat.stride(0), n
+        return flat, r
+
+    def _disc_ws(self, n):
+        nbytes = self.lib.hmmr_disc_pose_workspace_bytes(n)
+        return self._ws.setdefault("disc_pose", _Workspace(self.device)).get(nbytes), nbytes
+
+    def _disc_grads(self, bank, want_weights, g):
+        from .disc_bank import NAMES
+        names = NAMES if want_weights is True else (() if not want_weights else tuple(want_weights))
+        out = {n: (torch.empty(bank.params[n].shape, dtype=torch.float32, device=self.device) if n in names else None) for n in NAMES}
+        for n in NAMES:
+            setattr(g, "d_" + n, L.ptr(out[n]))
+        return out
+
+    def disc_pose(self, poses_a, poses_b=None):
+        """PoseDiscriminator.get_output on the bank (hmmr_disc_pose_fwd): two segments of pose rows (see _pose_rows; either may be
+        None or empty) -> out [n_a + n_b, 24], the rows of poses_a first.  Nothing is concatenated or copied."""
+        bank = self.disc_pose_bank()
+        ka, ra = self._pose_rows(poses_a, "poses_a")
+        kb, rb = self._pose_rows(poses_b, "poses_b")
+        n = ra.n + rb.n
+        out = torch.empty((n, 24), dtype=torch.float32, device=self.device)
+        ws, nbytes = self._disc_ws(n)
+        L.check(self.lib.hmmr_disc_pose_fwd(C.byref(bank.dw), C.byref(ra), C.byref(rb), out.data_ptr(), ws.data_ptr(), nbytes, self._stream()),
+                "hmmr_disc_pose_fwd")
+        return out
+
+    def disc_pose_backward(self, poses_a, poses_b, d_out, want_poses_a=True, want_poses_b=True, want_weights=True, full_a=False, full_b=False):
+        """The derivative of `disc_pose` (hmmr_disc_pose_bwd): the forward's inputs and d_out [n_a + n_b, 24] -> (d_poses_a [n_a,207]
+        or None, d_poses_b [n_b,207] or None, {name: gradient} in the bank's layouts).  want_weights: True, False or a collection of
+        the names wanted (disc_bank.NAMES); what is not wanted is None and its launches are not queued.  full_a / full_b: the
+        segment's gradient as [n,216] rows whose first nine values (the global rotation) are zeros."""
+        bank = self.disc_pose_bank()
+        ka, ra = self._pose_rows(poses_a, "poses_a")
+        kb, rb = self._pose_rows(poses_b, "poses_b")
+        n = ra.n + rb.n
+        d_out = self.to_device(d_out).reshape(n, 24)
+        d = L.DiscPoseBwdDesc()
+        d.rows_a, d.rows_b, d.d_out = ra, rb, d_out.data_ptr()
+        def grad_rows(want, r, full):
+            if not (want and r.n):
+                return None, None, 207
+            if full:                                         # [n,216] rows: zeros for the global rotation, the 207 values behind them
+                g = torch.zeros((r.n, 216), dtype=torch.float32, device=self.device)
+                return g, g.data_ptr() + 36, 216
+            g = torch.empty((r.n, 207), dtype=torch.float32, device=self.device)
+            return g, g.data_ptr(), 207
+        d_a, d.d_poses_a, d.ld_a = grad_rows(want_poses_a, ra, full_a)
+        d_b, d.d_poses_b, d.ld_b = grad_rows(want_poses_b, rb, full_b)
+        grads = self._disc_grads(bank, want_weights, d.grads)
+        ws, nbytes = self._disc_ws(n)
+        L.check(self.lib.hmmr_disc_pose_bwd(C.byref(bank.dw), C.byref(d), ws.data_ptr(), nbytes, self._stream()), "hmmr_disc_pose_bwd")
+        return d_a, d_b, grads
+
+    def pose_prior(self, real, fake, w_e=1.0, w_d=1.0, want_losses=True, want_d_rs=True, want_weights=True):
+        """The closed loop of one step on one recomputed forward (hmmr_pose_prior): mocap rows `real`, predicted rows `fake` ->
+        (losses [3] = e_pose, d_real, d_fake, d_rs_fake [n_fake,24,3,3] = w_e d e_pose / d Rs with a zero global rotation -- what
+        `smpl_backward` takes as d_rs --, {name: gradient of w_d d_pose} in the bank's layouts).  Each is None when not wanted."""
+        bank = self.disc_pose_bank()
+        ka, ra = self._pose_rows(real, "real")
+        kb, rb = self._pose_rows(fake, "fake")
+        d = L.PosePriorDesc()
+        d.real, d.fake, d.w_e, d.w_d = ra, rb, float(w_e), float(w_d)
+        losses = torch.empty((3,), dtype=torch.float32, device=self.device) if want_losses else None
+        d_rs = torch.empty((rb.n, 24, 3, 3), dtype=torch.float32, device=self.device) if want_d_rs else None
+        d.losses, d.d_rs_fake = L.ptr(losses), L.ptr(d_rs)
+        grads = self._disc_grads(bank, want_weights, d.grads)
+        ws, nbytes = self._disc_ws(ra.n + rb.n)
+        L.check(self.lib.hmmr_pose_prior(C.byref(bank.dw), C.byref(d), ws.data_ptr(), nbytes, self._stream()), "hmmr_pose_prior")
+        return losses, d_rs, grads
 
     def smpl(self, theta, beta, cams=None, want_rs=True):
         """theta [m,72], beta [m,10], cams [m,3] or None (row-major views with a

@@ -7,8 +7,11 @@ The reference's functions take no engine; here the last keyword of each is `engi
 and `set_engine` names the one used when it is left out.  Ground truth carries no gradient.  TensorFlow's reduction rule
 (tf.losses.*, SUM_BY_NONZERO_WEIGHTS with its safe division) is restated in include/hmmr_hip.h, "Trainer losses".
 
-Not here: compute_loss_e_fake / compute_loss_d_fake / compute_loss_d_real (the discriminators) and call_hmr_ief / hmr_ief (the
-IEF lives in HmmrEngine.ief)."""
+compute_loss_e_fake / compute_loss_d_fake / compute_loss_d_real take the discriminator's output (discriminators.PoseDiscriminator,
+disc_autograd.disc_pose_apply) and are plain tensor arithmetic on 24 values per row; the closed loop of a step, losses and both
+gradients in one call, is HmmrEngine.pose_prior (hmmr_pose_prior).
+
+Not here: call_hmr_ief / hmr_ief (the IEF lives in HmmrEngine.ief)."""
 from __future__ import annotations
 
 import torch
@@ -161,6 +164,21 @@ def compute_loss_shape(shapes, engine=None):
     engine = _eng(engine)
     s = _f32(engine, shapes).reshape(-1, 10)
     return _SeqLoss.apply(engine, s.shape[0], 1, 14, L.LOSS_SHAPE_PRIOR, 0, {}, (5,), False, None, None, None, s)[0][0]
+
+
+def compute_loss_e_fake(out_fake):
+    """mean over the rows of sum_24 (out - 1)^2 (src/ops.py: compute_loss_e_fake); out_fake [N,24]"""
+    return ((out_fake - 1) ** 2).sum(dim=1).mean()
+
+
+def compute_loss_d_fake(out_fake):
+    """mean over the rows of sum_24 out^2 (src/ops.py: compute_loss_d_fake)"""
+    return (out_fake ** 2).sum(dim=1).mean()
+
+
+def compute_loss_d_real(out_real):
+    """mean over the rows of sum_24 (out - 1)^2 (src/ops.py: compute_loss_d_real)"""
+    return ((out_real - 1) ** 2).sum(dim=1).mean()
 
 
 def compute_deltas_batched(poses_prev, poses_curr):

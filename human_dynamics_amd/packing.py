@@ -695,6 +695,22 @@ def pack_smpl(smpl, store, joint_type="cocoplus", split=True, impl=None):
     return sc
 
 
+def pack_disc_pose(w, store, dtype=L.HMMR_F32):
+    """D_pose/* checkpoint arrays -> hmmr_disc_pose_weights_t in ONE blob on the store's device (hmmr_pack_disc_pose; the layouts are
+    in include/hmmr_hip.h, "Pose discriminator").  The bank is HMMR_F32 only: every other dtype is refused."""
+    import ctypes as C
+    lib = L.load()
+    arr, n, keep = _vars_table({k: v for k, v in w.items() if k.startswith("D_pose/")})
+    dw = L.DiscPoseWeights()
+    try:
+        _c_pack(store, lib.hmmr_pack_disc_pose_bytes(arr, n, dtype),
+                lambda host, nb, base: lib.hmmr_pack_disc_pose(arr, n, dtype, host, nb, base, C.byref(dw)))
+    except L.HmmrError as e:          # (a mis-shaped checkpoint is the caller's ValueError, as in pack_ief)
+        raise ValueError(str(e))
+    del keep
+    return dw
+
+
 def pack_smpl_grad(smpl, store, joint_type="cocoplus"):
     """What hmmr_smpl_bwd needs beside SmplConsts -> SmplGradConsts: cocoplus_regressor as a CSR by vertex (hmmr_pack_smpl_grad; the
     first 14 columns for joint_type 'lsp', batch_smpl.py:81-82).  A blob of its own: HmmrEngine packs it on the first backward call."""

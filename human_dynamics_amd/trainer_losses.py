@@ -4,8 +4,10 @@ of the closed loop omega -> losses, d_omega (HmmrEngine.omega_loss_grad -> hmmr_
 hmmr_smpl_bwd).  The results are the reference's dictionary keys -- e_kp, e_joints, e_smpl, e_const, e_shape, with the
 future / past / present suffixes -- as device scalars that are differentiable in the raw omegas.
 
-Out of scope (README): the discriminators and e_pose, e_hallucinate, an optimiser, the backward of the IEF and of f_movie -- the
-gradient stops at omega."""
+compute_losses_prior (:989-1020) is the pose discriminator's closed loop (HmmrEngine.pose_prior -> hmmr_pose_prior,
+csrc/disc_pose.hip): e_pose, d_pose and e_shape.
+
+Out of scope (README): e_hallucinate, an optimiser, a trainer loop, the mocap loader."""
 from __future__ import annotations
 
 import torch
@@ -122,3 +124,50 @@ def compute_losses_deltas(engine, omegas_dict, gt, suffix_future="_dt_future", s
             cams[delta_t] = cam.reshape(B, T, 3)
     out.update(total=total, best_cam=cams, status=stat)
     return out
+
+
+class _PosePrior(torch.autograd.Function):
+    """(engine, real rows, fake rows, the bank's tensors...) -> (e_pose, d_pose), two outputs.  The forward call already holds both
+    gradients of unit weight: d e_pose / d fake and d d_pose / d bank.  e_pose does not reach the bank and d_pose does not reach the
+    poses: the reference's e_opt and d_opt differentiate with respect to the encoder's and the discriminator's variables only -- an
+    output whose cotangent is absent passes nothing on (not even zeros)."""
+
+    @staticmethod
+    def forward(ctx, engine, real, fake, *bank_tensors):
+        from .disc_bank import NAMES
+        need = ctx.needs_input_grad
+        want_w = [n for i, n in enumerate(NAMES) if need[3 + i]]
+        losses, d_rs, g = engine.pose_prior(real, fake.detach(), 1.0, 1.0, want_d_rs=bool(need[2]), want_weights=want_w)
+        ctx.shape, ctx.names, ctx.has_rs = fake.shape, want_w, d_rs is not None
+        ctx.set_materialize_grads(False)
+        ctx.save_for_backward(*([d_rs] if d_rs is not None else []), *[g[n] for n in want_w])
+        return losses[0], losses[1] + losses[2]
+
+    @staticmethod
+    def backward(ctx, g_e, g_d):
+        from .disc_bank import NAMES
+        saved = list(ctx.saved_tensors)
+        d_rs = saved.pop(0) if ctx.has_rs else None
+        d_fake = (d_rs * g_e).reshape(ctx.shape) if (d_rs is not None and g_e is not None) else None
+        by_name = dict(zip(ctx.names, saved)) if g_d is not None else {}
+        return (None, None, d_fake) + tuple((by_name[n] * g_d) if n in by_name else None for n in NAMES)
+
+
+def compute_losses_prior(engine, poses_real, pred_poses_all, pred_shapes_all, bank_tensors=None):
+    """compute_losses_prior of the trainer (src/trainer_sequence_fc.py:989-1020): poses_real [n_real, 216] (or [n_real,24,3,3]; or
+    [n_real, 207], the global rotation already dropped) mocap rotations, pred_poses_all a list of predicted Rs [.., 24,3,3] (or one tensor), pred_shapes_all the same of shapes [.., 10].
+    -> {e_pose, d_pose, e_shape}: device scalars of ONE call of the closed loop plus the shape prior.  e_pose is differentiable in
+    the predicted Rs (through tf_smpl.autograd.smpl_apply, .backward() reaches omega), d_pose in the bank's tensors that require a
+    gradient (.grad lands on engine.disc_pose_bank().tensors()); e_pose does not reach the bank and d_pose does not reach the poses,
+    as the reference's two var_lists have it.  The counts of real and fake rows need not be equal: each mean runs over its own rows."""
+    from . import ops
+    def cat(x, w):
+        """a lone tensor (or a list of one) passes through as a view: the C call reads the predicted Rs where smpl_apply left them"""
+        x = list(x) if isinstance(x, (list, tuple)) else [x]
+        return x[0].reshape(-1, w) if len(x) == 1 else torch.cat([t.reshape(-1, w) for t in x], 0)
+    fake = cat(pred_poses_all, 216)
+    real = poses_real if isinstance(poses_real, torch.Tensor) else engine.to_device(poses_real)
+    real = real.reshape(real.shape[0], -1)                  # (rows of 216 values, or of the 207 behind the global rotation)
+    tensors = engine.disc_pose_bank().tensors() if bank_tensors is None else list(bank_tensors)
+    e_pose, d_pose = _PosePrior.apply(engine, real, fake, *tensors)
+    return {"e_pose": e_pose, "d_pose": d_pose, "e_shape": ops.compute_loss_shape(cat(pred_shapes_all, 10), engine=engine)}

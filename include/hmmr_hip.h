@@ -638,6 +638,92 @@ int hmmr_hallucinator_bwd(const hmmr_hallucinator_weights_t* w, const hmmr_hallu
                           void* stream);
 
 /* ------------------------------------------------------------------------- *
+ * Pose discriminator (additive to ABI 19; csrc/disc_pose.hip): PoseDiscriminator (src/discriminators.py), the losses
+ * of src/ops.py:127-136 and compute_losses_prior (src/trainer_sequence_fc.py:989-1020), forward and derivative.  Per row the
+ * input is x[23][9], the rotation matrices of joints 1..23 (the global rotation is dropped, as in poses_comb[:, 1:]):
+ *     a1[j] = x[j] . C1 + bc1            h1 = relu(a1)      C1 [9][32]      (D_pose/D_conv1, a 1x1 conv: shared by the joints)
+ *     a2[j] = h1[j] . C2 + bc2           h2 = relu(a2)      C2 [32][32]     (D_pose/D_conv2)
+ *     out[j] = h2[j] . wj[j] + bj[j]     j = 0..22          wj [23][32]     (D_pose/pose_out_j{j}: one fc per joint)
+ *     a3 = flat(h2) . F1 + b1            h3 = relu(a3)      F1 [736][1024], flat index j*32 + c   (D_alljoints_fc1)
+ *     a4 = h3 . F2 + b2                  h4 = relu(a4)      F2 [1024][1024]                        (D_alljoints_fc2)
+ *     out[23] = h4 . fo + bo                                                                        (D_alljoints_out)
+ * relu'(0) = 0.  out is always [n][24] (the reference's tf.squeeze fails for one row).  With rows in two segments, real then fake:
+ *     e_pose = mean_fake sum_24 (out - 1)^2    d_real = mean_real sum_24 (out - 1)^2    d_fake = mean_fake sum_24 out^2
+ * and d_pose = d_fake + d_real, each mean over its own segment's rows (the reference needs equal counts; here either may be empty).
+ * The reference's slim.l2_regularizer(d_wd) fills a collection its gather_losses never reads: weight decay has no effect on
+ * d_loss, and none is built here.
+ * Rows come as two segments {ptr, ld, n}: ptr is the first of a row's 207 values, ld the floats from one row to the next (>= 207).
+ * A caller passes hmmr_smpl_fwd's Rs + 9 with ld = 216, and mocap rows the same way: nothing is concatenated or copied.  Row r
+ * of `out` / `d_out` is row r of rows_a for r < n_a, row r - n_a of rows_b otherwise.
+ * Bank (HMMR_F32 only, every other dtype is refused): plain [cout_pad][K] fp32 rows, the bias in `shift`, no `scale`, padding zero:
+ *     conv1.w [32][16] (K = 9, columns 9..15 zero)   conv2.w [32][32]   heads.w [32][32] (row j = wj[j], rows 23..31 zero; shift = bj)
+ *     fc1.w [1024][1024]: K = 736 is not a size hmmr_conv_gemm takes (a power of two), so its rows are padded with zeros to 1024
+ *     fc2.w [1024][1024]   fc_out.w [128][1024] (row 0 = fo, shift[0] = bo)
+ * Every `shift` is padded with zeros to a multiple of 128 floats.  Gradients have the bank's own layouts (padding written as
+ * zeros), so an optimiser step is elementwise.
+ * Contract:
+ *  - Nothing is kept between calls.  The backward recomputes the forward into its workspace by the routine hmmr_disc_pose_fwd
+ *    runs: h2 [n][1024] (736 used: fc1's input and the gate), h3, h4.  h1 is NOT kept: the front backward recomputes it from x.
+ *  - fc1 / fc2 / fc_out run through hmmr_conv_gemm with a fixed split-K of 4; the data gradients contract over the rows of the
+ *    untransposed bank in 8 fixed slices, the weight gradients over the batch rows in 4; bias gradients and the front's six
+ *    gradients are summed in double (per tile of 4 rows in row order, then the tiles in tile order) and rounded once.
+ *    No floating-point atomics: equal inputs give equal bytes, and a row's out / d_poses does not depend on the other rows.
+ *  - A NULL output is skipped and its launches are not queued; at least one output is required.
+ *  - Refused with -1 before anything is queued: null required pointers; a negative count or n_a + n_b <= 0; ld < 207 (of a
+ *    non-empty segment, of a wanted d_poses); a bank that is not HMMR_F32 or has a missing / scaled layer; a workspace that is
+ *    too small; no output asked for; in hmmr_pose_prior an empty fake segment when d_rs_fake or losses is wanted.
+ * ------------------------------------------------------------------------- */
+typedef struct { const float* ptr; int64_t ld; int n; } hmmr_rows_t;
+
+typedef struct {
+    int dtype;
+    hmmr_layer_t conv1, conv2, heads, fc1, fc2, fc_out;
+} hmmr_disc_pose_weights_t;
+
+typedef struct {                       /* the twelve gradients in the layouts of the bank itself; each may be NULL */
+    float* d_conv1;  float* d_bc1;     /* [32][16], [32] */
+    float* d_conv2;  float* d_bc2;     /* [32][32], [32] */
+    float* d_heads;  float* d_bj;      /* [32][32], [32] (rows / entries >= 23 written as zeros) */
+    float* d_fc1;    float* d_b1;      /* [1024][1024] (columns >= 736 written as zeros), [1024] */
+    float* d_fc2;    float* d_b2;      /* [1024][1024], [1024] */
+    float* d_fc_out; float* d_bo;      /* [128][1024], [128] (rows / entries >= 1 written as zeros) */
+} hmmr_disc_pose_grads_t;
+
+typedef struct {
+    hmmr_rows_t rows_a, rows_b;        /* the forward's inputs */
+    const float* d_out;                /* [n_a + n_b][24] */
+    float* d_poses_a; int64_t ld_a;    /* 207 values per row written at row stride ld, nothing else touched; or NULL */
+    float* d_poses_b; int64_t ld_b;
+    hmmr_disc_pose_grads_t grads;
+} hmmr_disc_pose_bwd_desc_t;
+
+typedef struct {
+    hmmr_rows_t real, fake;
+    float w_e, w_d;
+    float* losses;                     /* [3] = e_pose, d_real, d_fake: sums in double, in row order, rounded once; or NULL.  The loss
+                                          of an empty segment is 0 */
+    float* d_rs_fake;                  /* [n_fake][216] or NULL: nine zeros, then w_e * d e_pose / d x -- what hmmr_smpl_bwd reads as d_rs */
+    hmmr_disc_pose_grads_t grads;      /* the gradients of w_d * d_pose */
+} hmmr_pose_prior_desc_t;
+
+/* One layout for the three entry points below; 0 for n <= 0. */
+size_t hmmr_disc_pose_workspace_bytes(int n);
+/* out [n_a + n_b][24] */
+int hmmr_disc_pose_fwd(const hmmr_disc_pose_weights_t* w, const hmmr_rows_t* rows_a, const hmmr_rows_t* rows_b, float* out,
+                       void* ws, size_t ws_bytes, void* stream);
+int hmmr_disc_pose_bwd(const hmmr_disc_pose_weights_t* w, const hmmr_disc_pose_bwd_desc_t* desc, void* ws, size_t ws_bytes, void* stream);
+/* The closed loop of one step on ONE recomputed forward: the losses, and the only two gradients a step needs -- the encoder's
+ * (e_opt differentiates e_loss with respect to encoder variables only) and the discriminator's (d_opt: D_var only).  With
+ * s_e = (float)(2 w_e / n_fake), s_f = (float)(2 w_d / n_fake), s_r = (float)(2 w_d / n_real), the cotangents are
+ * s_e * (out - 1) on the fake rows, and s_r * (out - 1) on the real and s_f * out on the fake rows; each result is byte for
+ * byte what hmmr_disc_pose_fwd and two hmmr_disc_pose_bwd calls with those cotangents give.  Workspace:
+ * hmmr_disc_pose_workspace_bytes(n_real + n_fake).  Built for the rows of a training step (hundreds to a few thousand): the losses
+ * and the two cotangents come from ONE workgroup, whose last step adds the row sums one after the other -- the price of the row
+ * order.  Every count the checks admit (n_real + n_fake < 2^21) is computed correctly, but beyond some ten thousand rows that
+ * launch is a serial tail of milliseconds. */
+int hmmr_pose_prior(const hmmr_disc_pose_weights_t* w, const hmmr_pose_prior_desc_t* desc, void* ws, size_t ws_bytes, void* stream);
+
+/* ------------------------------------------------------------------------- *
  * SMPL forward + keypoint projection: SMPL.__call__ (src/tf_smpl/batch_smpl.py:
  * 89-162), batch_rodrigues / batch_global_rigid_transformation
  * (src/tf_smpl/batch_lbs.py:42-60, 133-194), batch_orth_proj_idrot
@@ -1229,6 +1315,11 @@ int hmmr_pack_hallucinator(const hmmr_var_t* vars, int n_vars, int dtype, void* 
 size_t hmmr_pack_ief_bytes(const hmmr_var_t* vars, int n_vars, int dtype, const int* delta_t, int n_delta);
 int hmmr_pack_ief(const hmmr_var_t* vars, int n_vars, int dtype, const int* delta_t, int n_delta, int num_stages, void* host_blob,
                   size_t blob_bytes, const void* device_base, hmmr_ief_weights_t* out);
+/* D_pose/D_conv1|D_conv2/weights [1,1,9,32] / [1,1,32,32], D_pose/pose_out_j{0..22}/weights [32,1], D_pose/D_alljoints_fc1|fc2|out/
+ * weights [736,1024] / [1024,1024] / [1024,1], each with its biases -> the bank of "Pose discriminator"; dtype must be HMMR_F32. */
+size_t hmmr_pack_disc_pose_bytes(const hmmr_var_t* vars, int n_vars, int dtype);
+int hmmr_pack_disc_pose(const hmmr_var_t* vars, int n_vars, int dtype, void* host_blob, size_t blob_bytes, const void* device_base,
+                        hmmr_disc_pose_weights_t* out);
 
 /* The body model in the src/tf_smpl layout (batch_smpl.py:35-80: what SMPL.__init__ builds from the pkl, or the checkpoint's own
  * non-trainable variables of the same names), fp32 host arrays */
