@@ -60,13 +60,13 @@ class TailDesc(C.Structure):
         ("h1", _vp), ("hin", C.c_int), ("win", C.c_int), ("w2", _vp), ("scale2", _fp), ("shift2", _fp),
         ("xp", _vp), ("wsc", _vp), ("shift_sc", _fp),
         ("conv2_stride", C.c_int), ("out_pre", _vp),
-        ("pair_stream", _vp), ("c_xp", C.c_int), ("unit_stream", _vp),
+        ("pair_stream", _vp), ("c_xp", C.c_int), ("unit_stream", _vp), ("trunk_keep_stride", C.c_int),
     ]
 
 
 class Debug(C.Structure):
     """hmmr_debug_t: development switches, all zero = product defaults."""
-    _fields_ = [("stem_route", C.c_int), ("stem_no_conv1", C.c_int), ("gemm_probe", C.c_int), ("smpl_blend_mfma", C.c_int), ("ief_no_group", C.c_int), ("reserved", C.c_int * 3),
+    _fields_ = [("stem_route", C.c_int), ("stem_no_conv1", C.c_int), ("gemm_probe", C.c_int), ("smpl_blend_mfma", C.c_int), ("ief_no_group", C.c_int), ("reserved", C.c_int * 2), ("keep_dead_rows", C.c_int),
                 ("pair_min_pixels", C.c_int), ("pair_two_tile_min", C.c_int), ("pair_form", C.c_int)]
 
 
@@ -116,7 +116,7 @@ END_CONV3_LAUNCH, END_TAIL_BF16, END_TAIL_BF16_STRIDE2, END_TAIL_SPLIT, END_B1_U
 class UnitPlan(C.Structure):
     """hmmr_unit_plan_t: what hmmr_resnet50_fwd launches for one unit (hmmr_resnet50_plan; host only)"""
     _fields_ = [(k, C.c_int) for k in ("shortcut", "conv1", "conv2", "end", "reads_fused_preact", "writes_raw", "writes_pre",
-                                       "pair_demoted", "swaps_t1_t2", "leaves_h1")]
+                                       "pair_demoted", "swaps_t1_t2", "leaves_h1", "trunk_keep_stride")]
 
 
 def resnet_plan(rw, n_total):
@@ -401,6 +401,7 @@ SIGNATURES = {
     "hmmr_bottleneck_tail": (C.c_int, [C.POINTER(TailDesc), _vp]),
     "hmmr_pair_stream_bytes": (C.c_size_t, [C.c_int, C.c_int, C.c_int]),
     "hmmr_b1_unit_stream_bytes": (C.c_size_t, [C.c_int]),
+    "hmmr_trunk_keep_launches": (C.c_ulonglong, [C.c_int]),
     "hmmr_conv3x3_stream_bytes": (C.c_size_t, [C.c_int, C.c_int]),
     "hmmr_conv1x1_stream_bytes": (C.c_size_t, [C.c_int, C.c_int]),
     "hmmr_mfma_rate_probe": (C.c_int, [C.c_int, C.c_int, _fp, _vp]),

@@ -26,8 +26,8 @@ extern "C" void hmmr_set_debug(const hmmr_debug_t* d) { g_debug = d ? *d : hmmr_
 extern "C" void hmmr_get_debug(hmmr_debug_t* d) { if (d) *d = g_debug; }
 
 // ---- launch counters (include/hmmr_hip.h: hmmr_launch_counts); `which` indexes hmmr_launch_counts_t's fields
-static std::atomic<unsigned long long> g_launches[10];       // 0 .. 4: hmmr_launch_counts_t, 5 .. 9: hmmr_stem_counts_t
-void hmmr_count_launch(int which) { if (which >= 0 && which < 10) g_launches[which].fetch_add(1ull, std::memory_order_relaxed); }
+static std::atomic<unsigned long long> g_launches[11];       // 0 .. 4: hmmr_launch_counts_t, 5 .. 9: hmmr_stem_counts_t, 10: hmmr_trunk_keep_launches
+void hmmr_count_launch(int which) { if (which >= 0 && which < 11) g_launches[which].fetch_add(1ull, std::memory_order_relaxed); }
 static void read_launches(int first, int count, unsigned long long* v, int clear) {
     for (int i = 0; i < count; ++i)
         v[i] = clear ? g_launches[first + i].exchange(0ull, std::memory_order_relaxed) : g_launches[first + i].load(std::memory_order_relaxed);
@@ -41,6 +41,11 @@ extern "C" void hmmr_stem_launch_counts(hmmr_stem_counts_t* out, int clear) {
     unsigned long long v[5];
     read_launches(5, 5, v, clear);
     if (out) { out->fused = v[0]; out->fused_conv1 = v[1]; out->repack = v[2]; out->gemm = v[3]; out->pool = v[4]; }
+}
+extern "C" unsigned long long hmmr_trunk_keep_launches(int clear) {
+    unsigned long long v;
+    read_launches(10, 1, &v, clear);
+    return v;
 }
 
 // compute units of the stream's device, asked once per device (csrc/common.h); 256 (an MI355X) if the runtime will not say

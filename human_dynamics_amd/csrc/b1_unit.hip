@@ -52,6 +52,7 @@ struct B1Args {
     bsplit_t* out_h1;                       // [M][64]
     int M, H, W, n_tiles;
     unsigned long long* ts;                 // probe build (bit 64): [tiles][4 waves][16] s_memtime stamps, or NULL
+    int keep;                               // hmmr_tail_desc_t.trunk_keep_stride: > 1, only the trunk rows x[:, ::keep, ::keep] reads are stored (stream_kit.h)
 };
 
 // Development build only (tools/b1_probe_build.sh, -DB1_PROBE_BITS=n): drop the MFMAs (1), the HBM traffic (2: every tile reads tile 0's
@@ -206,14 +207,17 @@ __global__ __launch_bounds__(256, 2) void b1_unit_kernel(const B1Args a) {
     bsplit_t* orow[4];
     bsplit_t* hrow[4];
     int ostep[4];
+    const unsigned lmask = trunk_live_mask(mbase, lane, a.H, W, a.keep);
 #pragma unroll
     for (int q = 0; q < 4; ++q) {
         const int r = 8 * q + rsub, m = mbase + r;
         const int ls = pslot ^ ((r >> 1) & 7);
         const bool ok = m < a.M && !B1_PROBE(2);
-        orow[q] = ok ? a.out + (long long)m * DEPTH + ls * 4 : (bsplit_t*)g_dump_page + lane * 4;
+        const bool live = ok && ((lmask >> r) & 1u);
+        orow[q] = live ? a.out + (long long)m * DEPTH + ls * 4
+                       : ok ? TRUNK_DEAD_ROW(wave, pslot * 4) : (bsplit_t*)g_dump_page + lane * 4;
         hrow[q] = ok ? a.out_h1 + (long long)m * 64 + ls * 4 : (bsplit_t*)g_dump_page + lane * 4;
-        ostep[q] = ok ? 32 : 0;
+        ostep[q] = live ? 32 : 0;
         rrow[q] = RES ? a.res + (long long)(ok ? m : 0) * a.ldr + ls * 4 : nullptr;
     }
     auto res_dma = [&](int chunk, int b) {
@@ -518,7 +522,7 @@ __global__ __launch_bounds__(256, 2) void b1_unit_kernel(const B1Args a) {
 #pragma unroll
         for (int q = 0; q < 4; ++q) xr[q] = *(const u32x4*)(stg + q * 1024 + lane16);
 #pragma unroll
-        for (int q = 0; q < 4; ++q) *(u32x4*)(hrow[q] + (ostep[q] ? j * 32 : 0)) = xr[q];
+        for (int q = 0; q < 4; ++q) *(u32x4*)(hrow[q] + ((mbase + 8 * q + rsub < a.M && !B1_PROBE(2)) ? j * 32 : 0)) = xr[q];
     }
     split_flag_max(satm);
     B1_STAMP(12);
@@ -560,7 +564,7 @@ int hmmr_b1_unit_split(const hmmr_tail_desc_t* d, hipStream_t stream) {
     a.scale3 = d->scale3; a.shift3 = d->shift3; a.pre_scale = d->pre_scale; a.pre_shift = d->pre_shift;
     a.res = (const bsplit_t*)d->res; a.ldr = d->ldr; a.out = (bsplit_t*)d->out;
     a.scale1 = d->scale1; a.shift1 = d->shift1; a.relu1 = d->relu1; a.out_h1 = (bsplit_t*)d->out_h1;
-    a.M = d->m; a.H = d->hin; a.W = d->win;
+    a.M = d->m; a.H = d->hin; a.W = d->win; a.keep = trunk_keep_of(d);
     if (B1_PROBE(64))       // (development build: the stamp buffer's address travels in the reserved debug words, like the other probe builds')
         a.ts = probe_stamp_buffer();
     return folded ? launch_b1<4, false>(a, stream) : launch_b1<0, true>(a, stream);

@@ -428,6 +428,10 @@ int hmmr_bottleneck_tail_split(const hmmr_tail_desc_t* d, hipStream_t stream);  
 
 extern "C" int hmmr_bottleneck_tail(const hmmr_tail_desc_t* d, void* stream) {
     HMMR_REQUIRE(d && (d->h2 || d->h1) && (d->w3 || d->pair_stream || d->unit_stream) && (d->res || d->xp), "hmmr_bottleneck_tail: null argument");
+    // trunk_keep_stride holds only where a kernel honours it: the unit pair and the block-1 unit (csrc/stream_kit.h), which write no out_pre
+    HMMR_REQUIRE(d->trunk_keep_stride >= 0 && (d->trunk_keep_stride <= 1 || (d->dtype == HMMR_F16X3 && (d->pair_stream || d->unit_stream) && !d->out_pre)),
+                 "hmmr_bottleneck_tail: trunk_keep_stride %d needs the f16x3 unit pair or block-1 unit (pair_stream / unit_stream) and no out_pre",
+                 d->trunk_keep_stride);
     if (d->dtype == HMMR_F16X3) return hmmr_bottleneck_tail_split(d, (hipStream_t)stream);
     const bool ph2 = d->w1 != nullptr;
     HMMR_REQUIRE(!ph2 || (d->out && d->pre_scale && d->pre_shift && d->scale1 && d->shift1 && d->out_h1 && !d->out_pre),

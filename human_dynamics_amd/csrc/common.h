@@ -45,6 +45,8 @@ const struct hmmr_debug_s* hmmr_debug_state();
 enum { HMMR_COUNT_UNIT_PAIR = 0, HMMR_COUNT_B1_UNIT = 1, HMMR_COUNT_TAIL_SPLIT = 2, HMMR_COUNT_CONV3X3_STREAM = 3, HMMR_COUNT_CONV1X1_STREAM = 4 };
 // ... and of the stem's launches (hmmr_stem_counts_t, field index + 5), counted where the pass issues them (csrc/resnet.hip: stem_run)
 enum { HMMR_COUNT_STEM_FUSED = 5, HMMR_COUNT_STEM_FUSED_CONV1 = 6, HMMR_COUNT_STEM_REPACK = 7, HMMR_COUNT_STEM_GEMM = 8, HMMR_COUNT_STEM_POOL = 9 };
+// ... and of the fused-unit launches queued with a keep stride > 1 (hmmr_trunk_keep_launches), counted beside the kernel family's counter
+enum { HMMR_COUNT_TRUNK_KEEP = 10 };
 void hmmr_count_launch(int which);
 
 // "has this (kernel, device) pair had its one-time hipFuncSetAttribute?"  One bit per device; a redundant call

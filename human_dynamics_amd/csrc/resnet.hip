@@ -247,6 +247,11 @@ static int plan_unit(const hmmr_resnet_weights_t* w, int u, int n, int H, const 
     const bool next_fused = !last && w->unit[u + 1].fuse_preact;
     const bool next_identity = !last && !w->unit[u + 1].shortcut.w;
     p.writes_raw = last || next_fused || next_identity;
+    // ... and WHICH ROWS of it are live.  A next unit with stride s > 1 and an identity shortcut (HMMR_SC_NONE) reads the raw trunk as
+    // x[:, ::s, ::s] (set_residual) -- and as nothing else once this unit's end has computed its conv1 (leaves_h1, below: no conv1 or
+    // shortcut launch pre-activates the trunk, and the unit after it reads the NEXT trunk).  The unit pair and the block-1 unit then
+    // store only those rows (hmmr_tail_desc_t.trunk_keep_stride); every other end, and every other successor, keeps them all
+    const int next_keep_stride = (next_identity && w->unit[u + 1].stride > 1) ? w->unit[u + 1].stride : 0;
     p.writes_pre = !last && !next_fused;
     // a register-resident unit pair (csrc/unit_pair.hip) is one round of 128-pixel workgroups with a ~20 k-cycle prologue however few
     // pixels there are: below ~12 k pixels (61 frames in block 3) the two launches it replaces are faster (profiles/r04_unit_pair_check.log:
@@ -294,6 +299,7 @@ static int plan_unit(const hmmr_resnet_weights_t* w, int u, int n, int H, const 
         p.end = w->dtype == HMMR_BF16 ? HMMR_END_TAIL_BF16 : pair ? HMMR_END_UNIT_PAIR :
                 (p.swaps_t1_t2 && U.unit_stream) ? HMMR_END_B1_UNIT : HMMR_END_TAIL_SPLIT;
         p.leaves_h1 = 1;
+        if (p.end == HMMR_END_UNIT_PAIR || p.end == HMMR_END_B1_UNIT) p.trunk_keep_stride = next_keep_stride;
     }
     *out = p;
     return 0;
@@ -473,7 +479,7 @@ static int resnet_fwd_t(const hmmr_resnet_weights_t* w, const float* images, int
                 }
                 if (p.shortcut == HMMR_SC_IN_TAIL) { t.xp = xin; t.wsc = U.shortcut.w; t.shift_sc = U.shortcut.shift; }
                 else if (!sc_in_c3) set_residual(t, res, U.depth, H, res_stride);
-                t.out = xn; t.pre_scale = N.pre_scale; t.pre_shift = N.pre_shift;
+                t.out = xn; t.pre_scale = N.pre_scale; t.pre_shift = N.pre_shift; t.trunk_keep_stride = p.trunk_keep_stride;
                 t.w1 = dt == HMMR_F16X3 ? U.w1n_frag : N.conv1.w;      // (not read with pair_stream)
                 t.scale1 = N.conv1.scale; t.shift1 = N.conv1.shift; t.relu1 = 1; t.n2 = N.base;
                 t.out_h1 = p.swaps_t1_t2 ? T2 : T1;

@@ -78,6 +78,40 @@ template <int OFF> __device__ __forceinline__ void lds_wr64(unsigned addr, unsig
 // a __device__ accessor it turns local and pc-relative, another instruction stream (profiles/stream_kit.log)
 static __device__ u32x4 g_dump_page[64 + 32] __attribute__((unused));
 
+// ---- dead trunk rows.  Ahead of a stride-2 unit with an identity shortcut the raw trunk has ONE reader, x[:, ::s, ::s] (resnet.hip:
+// plan_unit), so the producing launch is told the stride (hmmr_tail_desc_t.trunk_keep_stride) and row m = (img, y, x) of [.][H][W] is
+// LIVE iff y % s == 0 and x % s == 0.  A dead row in range takes the dump path for its TRUNK pointer only (same instructions, same
+// counted waits; its h1' row is stored as ever), but not to the page above: with 3 rows of 4 aimed at it every CU of an XCD would write
+// the same dozen L2 lines.  The region: one 128-byte line per wave -- line (workgroup % TRUNK_DEAD_WGS) * 4 + wave (the 32-pixel block
+// of the workgroup), a lane's 16 bytes at 16 * (lane & 7): the 8 lanes of a row piece that hold the same slot of different rows land
+// on each other, nobody reads it.  Workgroups are numbered in dispatch order and the chip holds at most 512 of these kernels' at once
+// (two per CU), so waves resident together -- on one CU or not -- never share a line.  512 KB: it stays in L2.  Rows beyond M keep
+// the page.  Declared and named like the page, for the same reason.
+#ifndef TRUNK_DEAD_SHARED_PAGE
+#define TRUNK_DEAD_SHARED_PAGE 0    /* A/B: 1 aims the dead rows at the dump page as well (measured: DESIGN.md section 5) */
+#endif
+constexpr int TRUNK_DEAD_WGS = 1024;
+static __device__ u32x4 g_dead_rows[TRUNK_DEAD_WGS * 4 * 8] __attribute__((unused));
+static_assert(sizeof(u32x4) * TRUNK_DEAD_WGS * 4 * 8 <= 512 * 1024, "the dead-row region lives in L2");
+// where a dead row's 16 bytes go: `wave` = the 32-pixel block of the workgroup, `dlane` = 4 * (lane & 7) (a macro: the kernels name the arrays)
+#define TRUNK_DEAD_ROW(wave, dlane) (TRUNK_DEAD_SHARED_PAGE ? (bsplit_t*)g_dump_page + lane * 4 \
+                                     : (bsplit_t*)g_dead_rows + (((int)blockIdx.x & (TRUNK_DEAD_WGS - 1)) * 4 + (wave)) * 32 + (dlane))
+// host: the keep stride a launch runs with -- the descriptor's (hmmr_bottleneck_tail has checked it), none under hmmr_debug_t.keep_dead_rows;
+// counted for hmmr_trunk_keep_launches.  Called once per launch, behind the entry's refusals
+static inline int trunk_keep_of(const hmmr_tail_desc_t* d) {
+    const int s = hmmr_debug_state()->keep_dead_rows ? 0 : d->trunk_keep_stride;
+    if (s > 1) hmmr_count_launch(HMMR_COUNT_TRUNK_KEEP);
+    return s;
+}
+// bit r: row mbase + r of a wave's 32 is live under keep stride s (every bit with s <= 1).  Lane L answers for row L & 31 -- one
+// pair of divisions per lane -- and a ballot collects the answers.  Once per tile, where the row pointers are set up: never in a chunk loop
+__device__ __forceinline__ unsigned trunk_live_mask(int mbase, int lane, int H, int W, int s) {
+    if (s <= 1) return ~0u;
+    asm volatile("" : "+s"(H), "+s"(W), "+s"(s));       // (made HERE, per tile: hoisted out of a persistent kernel's tile loop the divisors' reciprocals would sit in vector registers across its chunk loop)
+    const unsigned m = (unsigned)(mbase + (lane & 31)), rem = m % (unsigned)(H * W), y = rem / (unsigned)W, x = rem - y * (unsigned)W;
+    return (unsigned)__ballot(y % (unsigned)s == 0 && x % (unsigned)s == 0);
+}
+
 // ---- the staging tile: a 32 x 32 block of split values on its way from the MFMA's D layout (lane (lr, lh) = pixel lr, channels
 // 8 g + 4 lh .. + 3 of register group g) to 16-byte row stores.  32 rows (pixels) of 128 B = 8 slots of 16 B: slot 2 g = the hi halves of
 // group g's 8 channels, 2 g + 1 the lo halves, XOR-swizzled by sw = (lr >> 1) & 7.  Row piece q covers rows 8 q .. 8 q + 7: lane L holds

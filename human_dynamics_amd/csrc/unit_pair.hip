@@ -51,10 +51,11 @@ struct PairArgs {
     const float* scale1; const float* shift1; int relu1;
     bsplit_t* out_h1;                       // [M][N2]
     int M;
-    int tpw;                                // tiles (of 128 pixels) per workgroup (tiles b, b + grid, ...): 1, or more for the shapes with TWO (see the kernel)
+    int tpw;                               // tiles (of 128 pixels) per workgroup (tiles b, b + grid, ...): 1, or more for the shapes with TWO (see the kernel)
     float one;                              // 1.0f (a run-time value: see the epilogue)
     int probe;                              // always 0 in the product build (HMMR_GEMM_PROBE below)
     unsigned long long* ts;                 // probe build: [blocks][4 waves][8] s_memtime stamps, or NULL
+    int H, W, keep;                        // keep = hmmr_tail_desc_t.trunk_keep_stride: > 1, only the trunk rows x[:, ::keep, ::keep] of the H x W images reads are stored (stream_kit.h)
 };
 
 // Development build only (-DHMMR_GEMM_PROBE, tools/probe_build.sh): drop the MFMAs (1), the ring's DMA and waits (2), its barriers (4),
@@ -283,13 +284,22 @@ __global__ __launch_bounds__(256, 1) void unit_pair_kernel(const PairArgs a) {
     const bsplit_t* rrow[RES ? 4 : 1];
     bsplit_t* orow[4];
     int ostep[4];
+    // (RES: a keep stride comes with a shortcut tensor -- the folded form is refused one, and compiles to what it was)
+    unsigned lmask = ~0u;
+    int dlane = pslot * 4;                                     // this lane's 16 bytes of the wave's dead-row line
+    if constexpr (RES) {
+        lmask = trunk_live_mask(mbase, lane, a.H, a.W, a.keep);
+        asm volatile("" : "+v"(dlane));                        // (per tile, like the mask: nothing new lives across the chunk loop)
+    }
 #pragma unroll
     for (int q = 0; q < 4; ++q) {
         const int r = 8 * q + rsub, m = mbase + r;
         const int ls = pslot ^ ((r >> 1) & 7);
         const bool ok = m < a.M;
-        orow[q] = ok ? a.out + (long long)m * DEPTH + ls * 4 : (bsplit_t*)g_dump_page + lane * 4;
-        ostep[q] = ok ? 32 : 0;
+        const bool live = ok && ((lmask >> r) & 1u);
+        orow[q] = live ? a.out + (long long)m * DEPTH + ls * 4
+                       : ok ? TRUNK_DEAD_ROW(wave, dlane) : (bsplit_t*)g_dump_page + lane * 4;
+        ostep[q] = live ? 32 : 0;
         if constexpr (RES) rrow[q] = a.res + (long long)(ok ? m : 0) * a.ldr + ls * 4 + 32;
     }
     constexpr int NU = 4 * CL;                                 // units (two fragments, six MFMAs) per iteration
@@ -978,13 +988,18 @@ __global__ __launch_bounds__(512, 1) void unit_pair_ws_kernel(const PairArgs a) 
     const bsplit_t* rrow[4];                                   // where the next shortcut chunk is read (running)
     bsplit_t* orow[4];                                         // where the next trunk chunk goes
     int ostep[4];
+    const unsigned lmask = trunk_live_mask(mbase, lane, a.H, a.W, a.keep);
+    int dlane = pslot * 4;                                     // this lane's 16 bytes of the wave's dead-row line
+    asm volatile("" : "+v"(dlane));                            // (per tile, like the mask: nothing new lives across the chunk loop)
 #pragma unroll
     for (int q = 0; q < 4; ++q) {
         const int r = 8 * q + rsub, m = mbase + r;
         const int ls = pslot ^ ((r >> 1) & 7);
         const bool ok = m < a.M;
-        orow[q] = ok ? a.out + (long long)m * DEPTH + ls * 4 : (bsplit_t*)g_dump_page + lane * 4;
-        ostep[q] = ok ? 32 : 0;
+        const bool live = ok && ((lmask >> r) & 1u);
+        orow[q] = live ? a.out + (long long)m * DEPTH + ls * 4
+                       : ok ? TRUNK_DEAD_ROW(pr, dlane) : (bsplit_t*)g_dump_page + lane * 4;
+        ostep[q] = live ? 32 : 0;
         rrow[q] = a.res + (long long)(ok ? m : 0) * a.ldr + ls * 4;
     }
     auto dma_res = [&](char* tile, int ahead) {                // the shortcut chunk `ahead` chunks past rrow -> tile
@@ -1240,6 +1255,17 @@ int hmmr_unit_pair_split(const hmmr_tail_desc_t* d, hipStream_t stream) {
     const bool folded = d->xp != nullptr;
     HMMR_REQUIRE(folded != (d->res != nullptr), "hmmr_bottleneck_tail (f16x3, pair_stream): either a shortcut tensor (res) or a folded one (xp)");
     HMMR_REQUIRE(folded || d->ldr >= d->depth, "hmmr_bottleneck_tail: residual row stride < depth");
+    HMMR_REQUIRE(d->trunk_keep_stride <= 1 || (!folded && d->ho > 0 && d->wo > 0 && d->m % (d->ho * d->wo) == 0),
+                 "hmmr_bottleneck_tail (f16x3, pair_stream): trunk_keep_stride needs a shortcut tensor (res) and whole ho x wo images (got m = %d, %d x %d%s)",
+                 d->m, d->ho, d->wo, folded ? ", folded" : "");
+    const bool shape_b3 = d->c_mid == 256 && d->depth == 1024 && d->n2 == 256 && !folded;
+    const bool shape_b2 = d->c_mid == 128 && d->depth == 512 && d->n2 == 128 && !folded;
+    const bool shape_b2f = d->c_mid == 128 && d->depth == 512 && d->n2 == 128 && folded && d->c_xp == 256;
+    if (!shape_b3 && !shape_b2 && !shape_b2f) {
+        hmmr_set_error("hmmr_bottleneck_tail (f16x3, pair_stream): supported shapes are 256 -> 1024 -> 256 and 128 -> 512 -> 128 "
+                       "(the latter also with a folded 256-channel shortcut); got %d, %d, %d%s", d->c_mid, d->depth, d->n2, folded ? " folded" : "");
+        return -1;
+    }
     PairArgs a = {};
     a.src[0] = (const bsplit_t*)d->h2; a.src_ld[0] = d->c_mid;
     a.src[1] = (const bsplit_t*)d->xp; a.src_ld[1] = d->c_xp;
@@ -1247,6 +1273,7 @@ int hmmr_unit_pair_split(const hmmr_tail_desc_t* d, hipStream_t stream) {
     a.scale3 = d->scale3; a.shift3 = d->shift3; a.pre_scale = d->pre_scale; a.pre_shift = d->pre_shift;
     a.res = (const bsplit_t*)d->res; a.ldr = d->ldr; a.out = (bsplit_t*)d->out;
     a.scale1 = d->scale1; a.shift1 = d->shift1; a.relu1 = d->relu1; a.out_h1 = (bsplit_t*)d->out_h1; a.M = d->m; a.one = 1.0f;
+    a.H = d->ho; a.W = d->wo; a.keep = trunk_keep_of(d);
     a.probe = 0;
 #ifdef HMMR_GEMM_PROBE
     a.probe = hmmr_debug_state()->gemm_probe;
@@ -1256,12 +1283,7 @@ int hmmr_unit_pair_split(const hmmr_tail_desc_t* d, hipStream_t stream) {
     // EQUAL to the one-wave-per-SIMD form (profiles/r06_pair_ws_*: 0.252 against 0.260 ms in block 3, 0.334 against 0.333 in block 2,
     // standalone at 257 frames), so the round-4 form stays the default and hmmr_debug_t.pair_form = 2 selects this one (tests run both)
     const bool ws = hmmr_debug_state()->pair_form == 2;
-    if (d->c_mid == 256 && d->depth == 1024 && d->n2 == 256 && !folded)
-        return ws ? launch_pair_ws<16, 1024, 256>(a, stream) : launch_pair<16, 0, 1024, 256, true>(a, stream);
-    if (d->c_mid == 128 && d->depth == 512 && d->n2 == 128 && !folded)
-        return ws ? launch_pair_ws<8, 512, 128>(a, stream) : launch_pair<8, 0, 512, 128, true>(a, stream);
-    if (d->c_mid == 128 && d->depth == 512 && d->n2 == 128 && folded && d->c_xp == 256) return launch_pair<8, 16, 512, 128, false>(a, stream);
-    hmmr_set_error("hmmr_bottleneck_tail (f16x3, pair_stream): supported shapes are 256 -> 1024 -> 256 and 128 -> 512 -> 128 "
-                   "(the latter also with a folded 256-channel shortcut); got %d, %d, %d%s", d->c_mid, d->depth, d->n2, folded ? " folded" : "");
-    return -1;
+    if (shape_b3) return ws ? launch_pair_ws<16, 1024, 256>(a, stream) : launch_pair<16, 0, 1024, 256, true>(a, stream);
+    if (shape_b2) return ws ? launch_pair_ws<8, 512, 128>(a, stream) : launch_pair<8, 0, 512, 128, true>(a, stream);
+    return launch_pair<8, 16, 512, 128, false>(a, stream);
 }

@@ -27,15 +27,16 @@ DEFAULT_DTYPE = "f16x3"
 TILE_TABLES = os.path.join(os.path.dirname(os.path.abspath(__file__)), "tile_tables.json")
 
 
-def set_debug(stem_route=0, stem_no_conv1=0, gemm_probe=0, smpl_blend_mfma=0, ief_no_group=0, pair_min_pixels=0, pair_two_tile_min=0, pair_form=0):
+def set_debug(stem_route=0, stem_no_conv1=0, gemm_probe=0, smpl_blend_mfma=0, ief_no_group=0, pair_min_pixels=0, pair_two_tile_min=0, pair_form=0, keep_dead_rows=0):
     """Development switches of libhmmr_hip.so (hmmr_debug_t; process-wide, zeros = product defaults).
     pair_min_pixels: the unit-pair switch of hmmr_resnet50_fwd (0 = 12000 pixels, 1 = always the pair kernel, 2**31 - 1 = never);
     pair_two_tile_min: tiles from which a block-2 unit pair runs two tiles per workgroup (0 = 512, 1 = always, 2**31 - 1 = never);
-    pair_form: 0 = the one-wave-per-SIMD unit pair of round 4 (the default), 2 = the wave-specialised form of round 6 (two waves per SIMD; same bits)."""
+    pair_form: 0 = the one-wave-per-SIMD unit pair of round 4 (the default), 2 = the wave-specialised form of round 6 (two waves per SIMD; same bits);
+    keep_dead_rows: 1 = the fused-unit launches store every trunk row, also those only a stride-2 shortcut would skip (hmmr_tail_desc_t.trunk_keep_stride)."""
     d = L.Debug()
     d.stem_route, d.stem_no_conv1, d.gemm_probe = int(stem_route), int(stem_no_conv1), int(gemm_probe)
     d.smpl_blend_mfma, d.ief_no_group, d.pair_min_pixels = int(smpl_blend_mfma), int(ief_no_group), int(pair_min_pixels)
-    d.pair_two_tile_min, d.pair_form = int(pair_two_tile_min), int(pair_form)
+    d.pair_two_tile_min, d.pair_form, d.keep_dead_rows = int(pair_two_tile_min), int(pair_form), int(keep_dead_rows)
     L.load().hmmr_set_debug(C.byref(d))
 
 
@@ -1214,12 +1215,13 @@ class B1UnitCall(object):
       guard_rows: h1, xp and res are followed by that many rows of NaN halves, trunk and h1' by that many rows of PAIR_SENTINEL -- the
         valid rows of the outputs start as PAIR_SENTINEL too, not as zeros;
       stream: the device tensor of pack_b1_unit(...) if the caller has packed it already (host work);
-      three_launches: build the three hmmr_conv_gemm launches instead of the unit kernel (.h2 is their intermediate).
+      three_launches: build the three hmmr_conv_gemm launches instead of the unit kernel (.h2 is their intermediate);
+      keep_stride: hmmr_tail_desc_t.trunk_keep_stride of the unit kernel (> 1: only the trunk rows [:, ::s, ::s] are stored).
     .descs are the descriptors run() launches (a test may edit them), .trunk [M + guard_rows, 256] / .h1 [M + guard_rows, 64] the split
     outputs as rows of pixels, .grid = (n, h, w)."""
 
     def __init__(self, h1, conv2, w3_hwio, bias3, pre, w1_hwio, bn1, res=None, shortcut=None, relu1=True, res_ld=0, guard_rows=0,
-                 stream=None, three_launches=False, device="cuda:0"):
+                 stream=None, three_launches=False, keep_stride=0, device="cuda:0"):
         self.lib = L.load()
         dev = self.dev = torch.device(device)
         store = self.store = packing.DeviceStore(dev)
@@ -1317,7 +1319,7 @@ class B1UnitCall(object):
                 d.res, d.ldr = rt.data_ptr(), rt.shape[1]
             d.pre_scale, d.pre_shift = ps.data_ptr(), pb.data_ptr()
             d.scale1, d.shift1, d.relu1 = sc1.data_ptr(), b1.data_ptr(), int(bool(relu1))
-            d.out, d.out_h1 = self.trunk.data_ptr(), self.h1.data_ptr()
+            d.out, d.out_h1, d.trunk_keep_stride = self.trunk.data_ptr(), self.h1.data_ptr(), int(keep_stride)
             self.descs, self._call, self._what = [d], self.lib.hmmr_bottleneck_tail, "hmmr_bottleneck_tail (block-1 unit)"
 
     def run(self):
@@ -1339,11 +1341,13 @@ class UnitPairCall(object):
       guard_rows: every input is followed by that many rows of NaN halves, every output by that many rows of PAIR_SENTINEL -- and the
         valid rows of the outputs start as PAIR_SENTINEL too, not as zeros;
       stream: the device tensor of packing.pack_pair_stream([W3 | wsc_rows], W1) if the caller has packed it already (host work);
-      two_launches: build the two hmmr_conv_gemm launches instead of the pair.
+      two_launches: build the two hmmr_conv_gemm launches instead of the pair;
+      grid = (h, w), keep_stride: the rows are whole h x w images and hmmr_tail_desc_t.trunk_keep_stride of the pair (> 1: only the
+        trunk rows [:, ::s, ::s] are stored).
     .descs are the descriptors run() launches (a test may edit them), .trunk / .h1 the split outputs, guard rows included."""
 
     def __init__(self, h2, W3, bias3, pre, W1, bn1, res=None, shortcut=None, relu1=True, res_ld=0, guard_rows=0, stream=None,
-                 two_launches=False, device="cuda:0"):
+                 two_launches=False, grid=None, keep_stride=0, device="cuda:0"):
         self.lib = L.load()
         dev = self.dev = torch.device(device)
         store = self.store = packing.DeviceStore(dev)
@@ -1427,7 +1431,9 @@ class UnitPairCall(object):
                 t.res, t.ldr = rt.data_ptr(), rt.shape[1]
             t.pre_scale, t.pre_shift = ps.data_ptr(), pb.data_ptr()
             t.scale1, t.shift1, t.relu1, t.n2, t.out_h1 = sc1.data_ptr(), b1.data_ptr(), int(bool(relu1)), n2, self.h1.data_ptr()
-            t.pair_stream = self.stream.data_ptr()
+            t.pair_stream, t.trunk_keep_stride = self.stream.data_ptr(), int(keep_stride)
+            if grid is not None:
+                t.ho, t.wo = grid
             self.descs, self._call, self._what = [t], self.lib.hmmr_bottleneck_tail, "hmmr_bottleneck_tail (unit pair)"
 
     def run(self):

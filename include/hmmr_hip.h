@@ -31,7 +31,7 @@
 extern "C" {
 #endif
 
-#define HMMR_ABI_VERSION 19      /* 19: hmmr_clock_probe (measurement aid); 18: HMMR_FLAG_NAN, hmmr_debug_t.pair_form (the wave-specialised unit pair), the C-side packers hmmr_pack_*; 17: k_order = 2 on a 1x1 filter (the two-ring stream kernel of csrc/conv1x1_stream.hip, tiles 22 .. 26), hmmr_conv1x1_stream_bytes; 16: hmmr_tail_desc_t.unit_stream, hmmr_resnet_unit_t.unit_stream (the whole-unit kernel of block 1, csrc/b1_unit.hip), hmmr_b1_unit_stream_bytes, hmmr_debug_t.pair_min_pixels / pair_two_tile_min / launch counters, hmmr_resnet_unit_t.conv1_frag (block1/unit_1's conv1 inside the split stem); 15: k_order = 2 (the one-wave-per-SIMD 3x3 stream kernel, tiles 12 .. 18), hmmr_conv3x3_stream_bytes; 14: hmmr_tail_desc_t.pair_stream / c_xp, hmmr_resnet_unit_t.pair_stream (the register-resident unit pair of blocks 2-3), hmmr_run_flags; 13: hmmr_conv_desc_t.batch (grouped launches); 12: k_order = 1, 3x3 SAME convolutions out of an LDS-resident input patch (tiles 9, 10, 11) */
+#define HMMR_ABI_VERSION 19      /* 19: hmmr_clock_probe (measurement aid); also under 19 (the number is pinned by the test suite): hmmr_tail_desc_t.trunk_keep_stride and hmmr_unit_plan_t.trunk_keep_stride APPENDED to their structs (rebuild binders of hmmr_bottleneck_tail / hmmr_resnet50_plan), hmmr_debug_t.keep_dead_rows in the former reserved[2], hmmr_trunk_keep_launches; 18: HMMR_FLAG_NAN, hmmr_debug_t.pair_form (the wave-specialised unit pair), the C-side packers hmmr_pack_*; 17: k_order = 2 on a 1x1 filter (the two-ring stream kernel of csrc/conv1x1_stream.hip, tiles 22 .. 26), hmmr_conv1x1_stream_bytes; 16: hmmr_tail_desc_t.unit_stream, hmmr_resnet_unit_t.unit_stream (the whole-unit kernel of block 1, csrc/b1_unit.hip), hmmr_b1_unit_stream_bytes, hmmr_debug_t.pair_min_pixels / pair_two_tile_min / launch counters, hmmr_resnet_unit_t.conv1_frag (block1/unit_1's conv1 inside the split stem); 15: k_order = 2 (the one-wave-per-SIMD 3x3 stream kernel, tiles 12 .. 18), hmmr_conv3x3_stream_bytes; 14: hmmr_tail_desc_t.pair_stream / c_xp, hmmr_resnet_unit_t.pair_stream (the register-resident unit pair of blocks 2-3), hmmr_run_flags; 13: hmmr_conv_desc_t.batch (grouped launches); 12: k_order = 1, 3x3 SAME convolutions out of an LDS-resident input patch (tiles 9, 10, 11) */
 
 /* HMMR_F16X3: "split" tensors -- every group of 8 consecutive channels is 32 bytes, [hi x8][lo x8] with
  * hi = fp16(x), lo = fp16(x - hi), x clamped to +-65504 (4 bytes per element, 22 mantissa bits while lo is a normal
@@ -73,7 +73,10 @@ typedef struct hmmr_debug_s {
                               2 = the packed-FMA vector form (smpl_verts_kernel).  1 and 2 agree to one fp32 ulp, 0 with
                               them to ~1e-7 m */
     int ief_no_group;      /* 1: hmmr_ief_fwd runs the delta regressors one after the other instead of as grouped launches (same bits) */
-    int reserved[3];
+    int reserved[2];
+    int keep_dead_rows;    /* (was reserved[2]: the struct keeps its size) 1: every fused-unit launch stores every trunk row, whatever
+                              hmmr_tail_desc_t.trunk_keep_stride says -- the A/B of the dead-row stores in one process, and the tests' reference.
+                              Same bits in every row the pass reads */
     int pair_min_pixels;   /* hmmr_resnet50_fwd runs a register-resident unit pair (csrc/unit_pair.hip) as the two launches it replaces when
                               the unit has fewer pixels than this (same bits, faster for short batches): 0 = the default (12000 in block 2, 14000 in block 3),
                               1 = always the pair kernel, INT_MAX = never */
@@ -97,6 +100,10 @@ typedef struct {
     unsigned long long conv1x1_stream;  /* csrc/conv1x1_stream.hip (ABI 17) */
 } hmmr_launch_counts_t;
 void hmmr_launch_counts(hmmr_launch_counts_t* out, int clear);
+/* ... and how many of the unit_pair / b1_unit launches were queued with a trunk_keep_stride > 1 in force (hmmr_tail_desc_t; 3 per pass in
+ * the default f16x3 schedule at sizes where the pairs are on, 0 under hmmr_debug_t.keep_dead_rows).  A function of its own, with its own
+ * clear, so hmmr_launch_counts_t keeps its size. */
+unsigned long long hmmr_trunk_keep_launches(int clear);
 /* ... and of the stem's launches, wherever they were issued (hmmr_resnet50_fwd or hmmr_resnet50_stem); a struct of its own, so
  * hmmr_launch_counts_t keeps its size.  One pass adds 1 to `fused` OR `fused_conv1`, or 1 to each of `repack`, `gemm`, `pool`. */
 typedef struct {
@@ -363,6 +370,13 @@ typedef struct {
      * 0, 1 of each): A(0) | A(1) B(0) | A(2) B(1) | ... | A(7) B(6) | B(7) (the order of the kernel's software pipeline).  scale2 / shift2: conv2's folded BN as the k_order 2 layer carries it.  With xp (c_xp = 64; res == NULL)
      * conv3's K is {h2, xp}.  Bit-identical to hmmr_conv_gemm(k_order 2) + conv3 + conv1 as three launches. */
     const void* unit_stream;
+    /* HMMR_F16X3 with pair_stream or unit_stream: 0 or 1 = every row of `out` is stored.  s > 1: the caller promises that `out` is read
+     * only as x[:, ::s, ::s] of its [m / (ho * wo)][ho][wo][depth] images (unit_stream: hin x win) -- the strided identity shortcut of a
+     * stride-s unit whose conv1 this launch computes -- and the launch stores only those rows; the others keep what they held.  out_h1,
+     * the run flags and every stored row are the same bits.  Refused (nothing queued) on any other route, with out_pre, s < 0, or a
+     * pair_stream launch without whole ho x wo images.  hmmr_resnet50_fwd sets it where its plan says so (hmmr_unit_plan_t); a
+     * stand-alone caller's 0 keeps every row. */
+    int trunk_keep_stride;
 } hmmr_tail_desc_t;
 size_t hmmr_pair_stream_bytes(int kc3, int depth, int n2);
 size_t hmmr_b1_unit_stream_bytes(int c_xp);
@@ -434,6 +448,7 @@ typedef struct {
     int pair_demoted;                /* fewer pixels than hmmr_debug_t.pair_min_pixels: the two launches instead of the unit pair */
     int swaps_t1_t2;                 /* the tail wrote the next conv1 into the OTHER bottleneck buffer (conv2 ran inside it) */
     int leaves_h1;                   /* the next unit's conv1 is HMMR_CONV1_READY */
+    int trunk_keep_stride;           /* > 1: the end stores only the raw trunk rows x[:, ::s, ::s] (hmmr_tail_desc_t.trunk_keep_stride) */
 } hmmr_unit_plan_t;
 /* Host only: no HIP call, reads the same hmmr_debug_t as the pass.  n_total = n + n_zero.  -1: the table is inconsistent
  * (hmmr_last_error names the unit). */
