@@ -237,6 +237,16 @@ class SeqLossDesc(C.Structure):
                 ("ws", _vp), ("ws_bytes", C.c_size_t)]
 
 
+class AdamSeg(C.Structure):
+    """hmmr_adam_seg_t: one tensor of a TF Adam step (csrc/adam.hip); g NULL or n 0 = skipped"""
+    _fields_ = [("p", _fp), ("g", _fp), ("m", _fp), ("v", _fp), ("n", C.c_longlong)]
+
+
+class AdamHyper(C.Structure):
+    """hmmr_adam_hyper_t: the hyper-parameters of a step; the beta powers are the caller's float32 products"""
+    _fields_ = [(k, C.c_float) for k in ("lr", "beta1", "beta2", "eps", "beta1_power", "beta2_power")]
+
+
 class Var(C.Structure):
     """hmmr_var_t: one checkpoint variable for the C-side packers (csrc/pack.cpp)"""
     _fields_ = [("name", C.c_char_p), ("data", _fp), ("numel", C.c_int64)]
@@ -391,6 +401,10 @@ SIGNATURES = {
     "hmmr_omega_loss_grad_workspace_bytes": (C.c_size_t, [C.POINTER(SmplConsts), C.c_int, C.c_int]),
     "hmmr_omega_loss_grad": (C.c_int, [C.POINTER(SmplConsts), C.POINTER(SmplGradConsts), C.POINTER(SeqLossDesc), _fp, C.c_int, _fp, _fp,
                                        _vp, C.c_size_t, _vp]),
+    "hmmr_strip_mse_workspace_bytes": (C.c_size_t, [C.c_int]),
+    "hmmr_strip_mse": (C.c_int, [_fp, C.c_longlong, _fp, C.c_longlong, C.c_int, C.c_int, C.c_float, _fp, _fp, C.c_longlong, _fp, C.c_longlong,
+                                 _vp, C.c_size_t, _vp]),
+    "hmmr_adam_step": (C.c_int, [C.POINTER(AdamSeg), C.c_int, C.POINTER(AdamHyper), _vp]),
     "hmmr_crop_frames": (C.c_int, [_vp, _ip, C.c_int, C.c_int, C.c_int, _fp, _vp]),
     "hmmr_tube_augment": (C.c_int, [_vp, C.c_int, C.c_int, C.c_int, C.c_int, _ip, _vp, _fp, C.c_int, _fp, _vp]),
     "hmmr_track_workspace_bytes": (C.c_size_t, [C.c_int, C.c_int]),

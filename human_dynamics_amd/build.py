@@ -16,7 +16,7 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 INCLUDE = os.path.join(os.path.dirname(HERE), "include")
 LIB = os.path.join(HERE, "libhmmr_hip.so")
-SOURCES = ["api.cpp", "pack.cpp", "gemm_conv.hip", "conv3x3_stream.hip", "conv1x1_stream.hip", "stem.hip", "bottleneck.hip", "bottleneck_split.hip", "unit_pair.hip", "b1_unit.hip", "resnet.hip", "temporal.hip", "ief.hip", "ief_grad.hip", "movie_grad.hip", "disc_pose.hip", "smpl.hip", "smpl_grad.hip", "losses.hip", "eval_metrics.hip", "preprocess.hip", "tube.hip", "track.hip", "handoff.hip", "render.hip", "collage.hip", "person_view.hip", "windows.hip", "video_plan.cpp", "video.cpp", "probe.hip"]
+SOURCES = ["api.cpp", "pack.cpp", "gemm_conv.hip", "conv3x3_stream.hip", "conv1x1_stream.hip", "stem.hip", "bottleneck.hip", "bottleneck_split.hip", "unit_pair.hip", "b1_unit.hip", "resnet.hip", "temporal.hip", "ief.hip", "ief_grad.hip", "movie_grad.hip", "disc_pose.hip", "smpl.hip", "smpl_grad.hip", "losses.hip", "adam.hip", "eval_metrics.hip", "preprocess.hip", "tube.hip", "track.hip", "handoff.hip", "render.hip", "collage.hip", "person_view.hip", "windows.hip", "video_plan.cpp", "video.cpp", "probe.hip"]
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 # -fno-slp-vectorize (every file, round 5): under plain -O3 the SLP vectoriser packs adjacent scalar fp32 operations into v_pk_*_f32 with
 # op_sel shuffles.  In smpl_pose_kernel's kinematic chain that code produced WRONG translations for the last quarter of a wave (lanes
@@ -35,7 +35,7 @@ FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-fno-slp-vector
 # track.hip restates NumPy / SciPy float64 loops the same way, collage.hip the float64 passes of the resize oracle,
 # tube.hip the float32 operations of TF's resize and rotate kernels one by one, person_view.hip the float64 lines of compute_video_bbox
 EXTRA_FLAGS = {"pack.cpp": ["-ffp-contract=off"], "track.hip": ["-ffp-contract=off"], "collage.hip": ["-ffp-contract=off"],
-               "tube.hip": ["-ffp-contract=off"], "person_view.hip": ["-ffp-contract=off"]}
+               "tube.hip": ["-ffp-contract=off"], "person_view.hip": ["-ffp-contract=off"], "adam.hip": ["-ffp-contract=off"]}
 
 
 def _newer(src, dst):

@@ -438,3 +438,75 @@ extern "C" int hmmr_omega_loss_grad(const hmmr_smpl_consts_t* c, const hmmr_smpl
     HMMR_CHECK_HIP(hipGetLastError());
     return 0;
 }
+
+// ---- e_hallucinate ------------------------------------------------------- //
+// tf.losses.mean_squared_error(movie_strip, pred_movie_strip) with the default weight 1 (src/trainer_sequence_fc.py: e_hallucinate):
+// sum (a - b)^2 / (rows cols) over two [rows][cols] tensors, and both cotangents -- there is no stop-gradient on either side.
+// Two launches, no atomic: strip_mse_row_kernel, one workgroup per row -- thread t sums the elements t, t + 256, ... in index order in
+// fp64, the 256 partials fold pairwise (t += t + 128, then 64, ... 1: a fixed tree) into part[row], and the row's cotangents
+// d_a = weight 2 (a - b) / N (formed in fp64, rounded once) and d_b = -d_a (the same fp32 value negated) are written beside it;
+// strip_mse_sum_kernel, one thread: the rows in row order, one division by N, one rounding to fp32.
+static constexpr int MSE_THREADS = 256;
+
+__global__ __launch_bounds__(MSE_THREADS) void strip_mse_row_kernel(const float* __restrict__ a, long long lda, const float* __restrict__ b, long long ldb,
+                                                                     int cols, double scale, float* d_a, long long ld_da, float* d_b, long long ld_db,
+                                                                     double* __restrict__ part) {
+    __shared__ double sP[MSE_THREADS];
+    const int r = blockIdx.x, tid = threadIdx.x;
+    const float* ar = a + (long long)r * lda;
+    const float* br = b + (long long)r * ldb;
+    float* da = d_a ? d_a + (long long)r * ld_da : nullptr;
+    float* db = d_b ? d_b + (long long)r * ld_db : nullptr;
+    double s = 0.0;
+    for (int i = tid; i < cols; i += MSE_THREADS) {
+        const double d = (double)ar[i] - (double)br[i];
+        s += d * d;
+        const float g = (float)(scale * d);
+        if (da) da[i] = g;
+        if (db) db[i] = -g;
+    }
+    sP[tid] = s;
+    __syncthreads();
+    for (int w = MSE_THREADS / 2; w > 0; w >>= 1) {
+        if (tid < w) sP[tid] += sP[tid + w];
+        __syncthreads();
+    }
+    if (part && tid == 0) part[r] = sP[0];
+}
+
+__global__ void strip_mse_sum_kernel(const double* __restrict__ part, int rows, double inv_n, float* __restrict__ loss) {
+    if (blockIdx.x != 0 || threadIdx.x != 0) return;
+    double s = 0.0;
+    for (int r = 0; r < rows; ++r) s += part[r];
+    *loss = (float)(s * inv_n);
+}
+
+extern "C" size_t hmmr_strip_mse_workspace_bytes(int rows) {
+    if (rows <= 0) return 0;
+    WsCarver c;
+    c.take((size_t)rows * 8);
+    return c.total();
+}
+
+extern "C" int hmmr_strip_mse(const float* a, long long lda, const float* b, long long ldb, int rows, int cols, float weight, float* loss,
+                              float* d_a, long long ld_da, float* d_b, long long ld_db, void* ws, size_t ws_bytes, void* stream) {
+    HMMR_REQUIRE(a && b, "hmmr_strip_mse: null a or b");
+    HMMR_REQUIRE(rows > 0 && cols > 0, "hmmr_strip_mse: rows=%d and cols=%d must be positive", rows, cols);
+    HMMR_REQUIRE(rows <= (1 << 24), "hmmr_strip_mse: rows=%d exceed 2^24", rows);
+    HMMR_REQUIRE(lda >= cols && ldb >= cols, "hmmr_strip_mse: lda=%lld or ldb=%lld is below cols=%d", lda, ldb, cols);
+    HMMR_REQUIRE(loss || d_a || d_b, "hmmr_strip_mse: nothing to write (loss, d_a and d_b are all NULL)");
+    HMMR_REQUIRE((!d_a || ld_da >= cols) && (!d_b || ld_db >= cols), "hmmr_strip_mse: ld_da=%lld or ld_db=%lld is below cols=%d", ld_da, ld_db, cols);
+    HMMR_REQUIRE(__builtin_isfinite(weight), "hmmr_strip_mse: weight is not finite");
+    const size_t need = hmmr_strip_mse_workspace_bytes(rows);
+    HMMR_REQUIRE(!loss || (ws && ws_bytes >= need), "hmmr_strip_mse: workspace too small (%zu bytes given, %zu needed)", ws ? ws_bytes : (size_t)0, need);
+    hipStream_t s = (hipStream_t)stream;
+    const double N = (double)rows * (double)cols;
+    hipLaunchKernelGGL(strip_mse_row_kernel, dim3(rows), dim3(MSE_THREADS), 0, s, a, lda, b, ldb, cols, (double)weight * 2.0 / N, d_a, ld_da, d_b, ld_db,
+                       loss ? (double*)ws : (double*)nullptr);
+    HMMR_CHECK_HIP(hipGetLastError());
+    if (loss) {
+        hipLaunchKernelGGL(strip_mse_sum_kernel, dim3(1), dim3(64), 0, s, (const double*)ws, rows, 1.0 / N, loss);
+        HMMR_CHECK_HIP(hipGetLastError());
+    }
+    return 0;
+}

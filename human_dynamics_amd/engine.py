@@ -916,6 +916,45 @@ class HmmrEngine(object):
                 "hmmr_omega_loss_grad")
         return losses, (d_omega.reshape(shape) if shape is not None else d_omega), status, best_cam
 
+    def strip_mse(self, a, b, weight=1.0, want_loss=True, want_d_a=True, want_d_b=True):
+        """tf.losses.mean_squared_error of two [..., cols] fp32 device tensors of one shape (hmmr_strip_mse; the trainer's e_hallucinate):
+        -> (loss, a device scalar; d_a = weight 2 (a - b) / N and d_b = -d_a in the inputs' shape).  Each is None when not wanted.
+        2-D views with a unit inner stride are read in place."""
+        def rows(x):
+            if not (isinstance(x, torch.Tensor) and x.is_cuda and x.dtype == torch.float32):
+                x = self.to_device(x)
+            if not (x.dim() == 2 and x.stride(1) == 1 and (x.shape[0] == 1 or x.stride(0) >= x.shape[1])):
+                x = x.contiguous().reshape(-1, x.shape[-1])
+            return x
+        shape = tuple(a.shape)
+        if tuple(b.shape) != shape or len(shape) == 0:
+            raise ValueError("strip_mse: two tensors of one shape [..., cols], got %s and %s" % (shape, tuple(b.shape)))
+        a, b = rows(a), rows(b)
+        n, c = a.shape
+        ld = lambda x: x.stride(0) if n > 1 else c
+        loss = torch.empty((), dtype=torch.float32, device=self.device) if want_loss else None
+        d_a = torch.empty((n, c), dtype=torch.float32, device=self.device) if want_d_a else None
+        d_b = torch.empty((n, c), dtype=torch.float32, device=self.device) if want_d_b else None
+        nbytes = self.lib.hmmr_strip_mse_workspace_bytes(n)
+        ws = self._ws.setdefault("strip_mse", _Workspace(self.device)).get(nbytes)
+        L.check(self.lib.hmmr_strip_mse(a.data_ptr(), ld(a), b.data_ptr(), ld(b), n, c, float(weight), L.ptr(loss), L.ptr(d_a), c, L.ptr(d_b), c,
+                                        ws.data_ptr(), nbytes, self._stream()), "hmmr_strip_mse")
+        return loss, (d_a.reshape(shape) if d_a is not None else None), (d_b.reshape(shape) if d_b is not None else None)
+
+    def adam_step(self, segments, lr, beta1, beta2, epsilon, beta1_power, beta2_power):
+        """One tf.train.AdamOptimizer step over `segments` in ONE call (hmmr_adam_step, csrc/adam.hip): an iterable of (p, g, m, v)
+        contiguous fp32 device tensors of equal element counts, updated in place; g None = a variable without a gradient, which keeps
+        its bytes.  The beta powers are the caller's float32 products of the step (optim.TFAdam owns them)."""
+        segs = list(segments)
+        table = (L.AdamSeg * max(len(segs), 1))()
+        for i, (p, g, m, v) in enumerate(segs):
+            for t in (p, m, v) + ((g,) if g is not None else ()):
+                if not (t.is_cuda and t.dtype == torch.float32 and t.is_contiguous() and t.numel() == p.numel()):
+                    raise ValueError("adam_step: segment %d needs contiguous fp32 device tensors of one element count" % i)
+            table[i].p, table[i].g, table[i].m, table[i].v, table[i].n = p.data_ptr(), L.ptr(g), m.data_ptr(), v.data_ptr(), p.numel()
+        h = L.AdamHyper(float(lr), float(beta1), float(beta2), float(epsilon), float(beta1_power), float(beta2_power))
+        L.check(self.lib.hmmr_adam_step(table, len(segs), C.byref(h), self._stream()), "hmmr_adam_step")
+
     def smpl_into(self, theta, beta, cams, rec, off_verts, off_joints, off_kps, off_rs):
         """SMPL forward that writes instance i's verts/joints/kps/Rs straight into row i of
         the packed record tensor `rec` [m, rec_len] at the given float offsets

@@ -11,6 +11,8 @@ compute_loss_e_fake / compute_loss_d_fake / compute_loss_d_real take the discrim
 disc_autograd.disc_pose_apply) and are plain tensor arithmetic on 24 values per row; the closed loop of a step, losses and both
 gradients in one call, is HmmrEngine.pose_prior (hmmr_pose_prior).
 
+mean_squared_error is tf.losses.mean_squared_error as the trainer uses it for e_hallucinate (HmmrEngine.strip_mse -> hmmr_strip_mse).
+
 Not here: call_hmr_ief / hmr_ief (the IEF lives in HmmrEngine.ief)."""
 from __future__ import annotations
 
@@ -164,6 +166,36 @@ def compute_loss_shape(shapes, engine=None):
     engine = _eng(engine)
     s = _f32(engine, shapes).reshape(-1, 10)
     return _SeqLoss.apply(engine, s.shape[0], 1, 14, L.LOSS_SHAPE_PRIOR, 0, {}, (5,), False, None, None, None, s)[0][0]
+
+
+class _StripMse(torch.autograd.Function):
+    """(engine, labels, predictions) -> the mean squared difference; the forward call already holds both unit-weight cotangents"""
+
+    @staticmethod
+    def forward(ctx, engine, a, b):
+        need = ctx.needs_input_grad
+        loss, d_a, d_b = engine.strip_mse(a.detach(), b.detach(), 1.0, want_d_a=bool(need[1]), want_d_b=bool(need[2]))
+        ctx.has = (d_a is not None, d_b is not None)
+        ctx.save_for_backward(*[d for d in (d_a, d_b) if d is not None])
+        return loss
+
+    @staticmethod
+    def backward(ctx, g):
+        saved = list(ctx.saved_tensors)
+        d_a = saved.pop(0) * g if ctx.has[0] else None
+        d_b = saved.pop(0) * g if ctx.has[1] else None
+        return None, d_a, d_b
+
+
+def mean_squared_error(labels, predictions, engine=None):
+    """tf.losses.mean_squared_error(labels, predictions) with the default weight: mean((labels - predictions)^2) over all elements of
+    two tensors of one shape [..., cols] (the trainer's e_hallucinate on two [B, T, 2048] movie strips; hmmr_strip_mse).  Unlike the
+    losses above it is differentiable in BOTH arguments: the reference puts no stop-gradient on the movie strip."""
+    engine = _eng(engine)
+    a, b = _f32(engine, labels), _f32(engine, predictions)
+    if a.shape != b.shape or a.numel() == 0:
+        raise ValueError("mean_squared_error: two non-empty tensors of one shape, got %s and %s" % (tuple(a.shape), tuple(b.shape)))
+    return _StripMse.apply(engine, a, b)
 
 
 def compute_loss_e_fake(out_fake):

@@ -7,7 +7,8 @@ future / past / present suffixes -- as device scalars that are differentiable in
 compute_losses_prior (:989-1020) is the pose discriminator's closed loop (HmmrEngine.pose_prior -> hmmr_pose_prior,
 csrc/disc_pose.hip): e_pose, d_pose and e_shape.
 
-Out of scope (README): e_hallucinate, an optimiser, a trainer loop, the mocap loader."""
+e_hallucinate is ops.mean_squared_error; the optimiser is optim.TFAdam and the step that composes all of this
+trainer_sequence_fc.HMRSequenceTrainer.  Out of scope (README): the tfrecord and mocap loaders."""
 from __future__ import annotations
 
 import torch

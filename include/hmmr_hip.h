@@ -937,6 +937,44 @@ int hmmr_omega_loss_grad(const hmmr_smpl_consts_t* c, const hmmr_smpl_grad_const
                          const float* omega, int use_optcam, float* losses, float* d_omega,
                          void* ws, size_t ws_bytes, void* stream);
 
+/* e_hallucinate (additive to ABI 19; csrc/losses.hip): tf.losses.mean_squared_error(movie_strip, pred_movie_strip) with its default
+ * weight 1 (src/trainer_sequence_fc.py; SUM_BY_NONZERO_WEIGHTS over a scalar weight divides by the element count) -- there is no
+ * stop-gradient, so the loss reaches both of its arguments.  a and b are [rows][cols] with row strides lda, ldb (floats):
+ *   loss = sum (a - b)^2 / N, N = rows cols;   d_a = weight 2 (a - b) / N;   d_b = -d_a.
+ * Summation order (fp64 on the fp32 inputs, no atomic; the same inputs give the same bytes): per row, thread t of 256 sums the
+ * elements t, t + 256, ... in index order and the 256 partials fold pairwise (t += t + 128, then 64, ... 1); then the rows in row
+ * order; one division by N and one rounding to fp32 -- `loss` is one fp32 device value, as the slots of hmmr_seq_loss_desc_t.losses.
+ * d_a = (float)(weight 2 / N x (a - b)) with the product in fp64; d_b is that fp32 value negated.  loss, d_a (row stride ld_da) and
+ * d_b (ld_db) may each be NULL and are then never written; `weight` scales the cotangents only.  The workspace (rows doubles) is
+ * needed with `loss` alone.  Refused before any launch: a null a or b; rows or cols <= 0; rows > 2^24; a row stride below cols;
+ * all three outputs NULL; a weight that is not finite; with `loss`, a workspace that is NULL or too small. */
+size_t hmmr_strip_mse_workspace_bytes(int rows);          /* 0 for rows <= 0 */
+int hmmr_strip_mse(const float* a, long long lda, const float* b, long long ldb, int rows, int cols, float weight, float* loss,
+                   float* d_a, long long ld_da, float* d_b, long long ld_db, void* ws, size_t ws_bytes, void* stream);
+
+/* ------------------------------------------------------------------------- *
+ * TF Adam (additive to ABI 19; csrc/adam.hip): one step of tf.train.AdamOptimizer over a list of tensors, as the published
+ * TF 1.x ApplyAdam kernel states it, operation by operation in float32 (this is NOT torch.optim.Adam: epsilon is added to sqrt(v)
+ * before the bias correction is folded into the step size, and the beta powers are float32 values multiplied once per step):
+ *   on the host:  alpha = lr * sqrtf(1 - beta2_power) / (1 - beta1_power)
+ *   per element:  m += (g - m) * (1 - beta1);   v += (g * g - v) * (1 - beta2);   p -= (m * alpha) / (sqrtf(v) + eps)
+ * with 1 - beta1 and 1 - beta2 formed once in float32.  beta1_power / beta2_power are beta^t of step t = 1, 2, ...: the caller owns
+ * them and multiplies them by beta AFTER the step (AdamOptimizer._finish).  The file is compiled without contraction, the division
+ * and the square root are the correctly rounded ones: the result is held to the bytes of a float32 NumPy restatement
+ * (tests/adam_cases.py).  Agreement with a TensorFlow binary is unmeasured.
+ *
+ * segs: a HOST array of device pointers, each 4-byte aligned.  A segment with g == NULL or n == 0 is skipped and its p, m and v keep
+ * their bytes (TF's treatment of a variable without a gradient).  One launch per 64 active segments, their descriptors as kernel
+ * arguments; a segment whose four pointers are all 16-byte aligned moves 16 bytes per lane, any other 4.  No atomic: the same
+ * inputs give the same bytes, and a value does not depend on how the tensors are cut into segments.  Segments must not overlap.
+ * Refused before anything is queued (-1, message in hmmr_last_error): null h; n_segs < 0, or a null table with n_segs > 0; a
+ * hyper-parameter that is not finite; a beta power outside (0, 1); n < 0 or n > 2^40; a NULL p, m or v with n > 0; a pointer of an
+ * active segment that is not 4-byte aligned.
+ * ------------------------------------------------------------------------- */
+typedef struct { float* p; const float* g; float* m; float* v; long long n; } hmmr_adam_seg_t;
+typedef struct { float lr, beta1, beta2, eps, beta1_power, beta2_power; } hmmr_adam_hyper_t;
+int hmmr_adam_step(const hmmr_adam_seg_t* segs, int n_segs, const hmmr_adam_hyper_t* h, void* stream);
+
 /* ------------------------------------------------------------------------- *
  * Crop before the path (process_image, src/evaluation/run_video.py:56-107; resize_img,
  * src/util/common.py:7-14): frames [n,h,w,3] uint8 -> out [n,224,224,3] fp32 in [-1,1].
